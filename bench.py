@@ -10,8 +10,14 @@ synthetic shard (weak scaling: per-GPU work fixed as N grows); random-init weigh
 batch 500, embedding 128, G/D (256, 256), pack 10.  One rank per GPU; the data plane is
 RCCL (``nccl``) for N > 1.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K rounds and prints the result line.  ``--full`` adds what the
+headline figure does not need: the Avg_JSD / Avg_WD evaluation of the last synthetic table (``avg_jsd`` /
+``avg_wd`` are null without it).  ``--dump-outputs DIR`` writes what the last timed round handed to its
+caller (``DIR/model_flat.npy``, ``DIR/synthetic_table.npy``, ``DIR/losses.npy``); every input is seeded,
+so two builds run with the same arguments can be compared output for output.
 
 Without ``WORLD_SIZE`` in the environment and ``--gpus N > 1`` the script is its own launcher
 (the reference's intended one-command single-node fan-out, `Server/dtds/distributed.py:956-971`):
@@ -48,7 +54,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--backend", default="auto")
     ap.add_argument("--gmm", default="torch")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--no-eval", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: Avg_JSD / Avg_WD of the last synthetic table "
+                         "against the clients' rows (avg_jsd / avg_wd in the result line; null without --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed rounds, write what the last timed round computed as DIR/<name>.npy: the "
+                         "aggregated model, the decoded synthetic table and the last-step losses")
+    ap.add_argument("--no-eval", action="store_true", help="with --full: skip the Avg_JSD / Avg_WD evaluation")
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--sync-csv", action="store_true", help="write each epoch CSV inside its round")
     ap.add_argument("--device-reset-at-exit", action="store_true",
@@ -163,6 +175,55 @@ def _rccl_transport(d: str | None) -> dict:
     return out
 
 
+# ----------------------------------------------------------------------------- outputs
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000    # all of DIR/*.npy together stay below this
+
+
+def _capture_tables(rt) -> dict:
+    """Keep a reference to the decoded table of every epoch CSV the federator writes (--dump-outputs): the
+    writer receives the very array the round produced, so nothing is copied or recomputed in the timed rounds."""
+    seen = {}
+    body = rt._write_epoch_csv_body
+
+    def capture(values, epoch):
+        seen.clear()
+        seen[epoch] = values
+        return body(values, epoch)
+
+    rt._write_epoch_csv_body = capture
+    return seen
+
+
+def _dump_outputs(d: str, rt, tables: dict, last_epoch: int) -> None:
+    """DIR/model_flat.npy (every G / D parameter and BN statistic after the last aggregation, float32),
+    DIR/synthetic_table.npy (the decoded rows behind the last epoch CSV; a fixed seeded row sample when the whole
+    table would not fit the budget) and DIR/losses.npy (loss_d, loss_g of the last step, float64)."""
+    import numpy as np
+    from fed_tgan_amd.utils.devsync import PendingHost
+
+    def plain(a):
+        a = np.asarray(a)
+        return np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+
+    os.makedirs(d, exist_ok=True)
+    flat = plain(rt.engine.flat.detach().float().cpu().numpy())
+    losses = np.asarray(rt.round_losses(), dtype=np.float64)
+    if last_epoch not in tables:
+        raise SystemExit(f"bench.py: --dump-outputs: no table was written for the last timed round ({last_epoch})")
+    table = tables[last_epoch]
+    table = plain(table.get() if isinstance(table, PendingHost) else table)
+    room = DUMP_BUDGET_BYTES - flat.nbytes - losses.nbytes - 3 * 1024     # (.npy headers)
+    if room <= 0:
+        raise SystemExit("bench.py: --dump-outputs: the model alone exceeds the output budget")
+    row_bytes = max(table[0:1].nbytes, 1)
+    if table.nbytes > room:
+        keep = np.sort(np.random.default_rng(0).choice(table.shape[0], size=room // row_bytes, replace=False))
+        table = table[keep]
+    np.save(os.path.join(d, "model_flat.npy"), flat)
+    np.save(os.path.join(d, "synthetic_table.npy"), table)
+    np.save(os.path.join(d, "losses.npy"), losses)
+
+
 # ----------------------------------------------------------------------------- one rank
 def run_rank(args) -> None:
     import torch
@@ -222,6 +283,7 @@ def run_rank(args) -> None:
             native.require().set_tuning(k, int(v))
     rt = FedRuntime(cfg, comm, device)
     rt.initialize()
+    tables = _capture_tables(rt) if (args.dump_outputs and rank == 0) else None
     for ep in range(args.warmup):
         rt.run_round(ep)
     rt.flush_writes()
@@ -242,6 +304,8 @@ def run_rank(args) -> None:
     last = os.path.join(out, f"{spec.name}_result", f"{spec.name}_synthesis_epoch_{cfg.epochs - 1}.csv")
 
     rt.timer.resolve(block=True)
+    if tables is not None:
+        _dump_outputs(args.dump_outputs, rt, tables, cfg.epochs - 1)
     check = args.check if args.check is not None else world > 1
     consistency = None
     if check:
@@ -255,7 +319,7 @@ def run_rank(args) -> None:
             raise SystemExit(f"bench.py: ranks disagree on the aggregate: {digests}")
 
     avg_jsd = avg_wd = None
-    if rank == 0 and not args.no_eval:
+    if rank == 0 and args.full and not args.no_eval:
         from fed_tgan_amd.data.synthetic import generate
         from fed_tgan_amd.eval.similarity import stat_sim
         import pandas as pd

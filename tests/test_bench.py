@@ -33,10 +33,32 @@ def test_bench_single_process():
     assert rec["value"] > 0 and abs(rec["ms_per_step"] - 1000 * rec["value"]) < 1e-2
 
 
+def test_bench_plain_run_dumps_outputs_and_skips_eval(tmp_path):
+    """A plain run (no --full) leaves the evaluation out; --dump-outputs writes the last timed round's
+    aggregated model, decoded table and losses as float32 / float64 .npy files."""
+    import numpy as np
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup",
+                        "0", "--rows", "1000", "--n-sample", "700", "--quiet", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=300, env=_env(), cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = _json_lines(r.stdout)[0]
+    assert KEYS <= set(rec) and rec["steps"] == 2 and rec["epochs_trained"] == 2
+    assert rec["avg_jsd"] is None and rec["avg_wd"] is None
+    assert sorted(os.listdir(d)) == ["losses.npy", "model_flat.npy", "synthetic_table.npy"]
+    out = {n: np.load(d / f"{n}.npy") for n in ("losses", "model_flat", "synthetic_table")}
+    for a in out.values():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all()
+    assert out["losses"].shape == (2,) and out["model_flat"].ndim == 1 and out["model_flat"].size > 10000
+    assert out["synthetic_table"].shape == (700, 42)           # every Intrusion column, decoded
+    assert sum(a.nbytes for a in out.values()) <= 64 * 1000 * 1000
+
+
 def test_bench_torchrun_two_ranks():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29561", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "1", "--warmup", "1", "--rows", "1000", "--n-sample", "1500", "--quiet"]
+           "--gpus", "2", "--steps", "1", "--warmup", "1", "--rows", "1000", "--n-sample", "1500", "--quiet",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=_env(), cwd="/tmp")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
