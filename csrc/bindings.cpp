@@ -1020,6 +1020,100 @@ void rng_bump(const Tensor& ctr) {
   fedtgan::launch_rng_bump(reinterpret_cast<uint64_t*>(ctr.data_ptr<int64_t>()), cur_stream());
 }
 
+// ----------------------------------------------------------------------------- conditional generation
+// the request buffers of kernels/cond_gen.hip (CondReq), validated: every table on the device, one entry per bin
+fedtgan::CondReq cond_req(const Tensor& drive, const Tensor& bin_opt, const Tensor& bin_code, const Tensor& quota,
+                          const Tensor& filled, const Tensor& seg_off, const Tensor& fixed_j, const Tensor& fixed_code,
+                          const Tensor& stats) {
+  const int64_t nb = bin_opt.numel(), nf = fixed_j.numel();
+  TORCH_CHECK(nb >= 1 && nb <= fedtgan::COND_MAX_BINS, "conditional request: 1..", fedtgan::COND_MAX_BINS, " bins, got ", nb);
+  auto i32 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(); };
+  auto i64 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(); };
+  auto f64 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kDouble && t.is_contiguous(); };
+  TORCH_CHECK(i32(drive) && drive.numel() == 2 && i32(bin_opt) && i32(fixed_j), "conditional request: int32 tables");
+  TORCH_CHECK(f64(bin_code) && bin_code.numel() == nb && f64(fixed_code) && fixed_code.numel() == nf,
+              "conditional request: float64 codes, one per bin / fixed column");
+  TORCH_CHECK(i64(quota) && quota.numel() == nb && i64(filled) && filled.numel() == nb && i64(seg_off) &&
+                  seg_off.numel() == nb && i64(stats) && stats.numel() == 2,
+              "conditional request: int64 quota / filled / seg_off per bin and two statistics");
+  fedtgan::CondReq r{};
+  r.drive = drive.data_ptr<int>();
+  r.n_bins = (int)nb;
+  r.bin_opt = bin_opt.data_ptr<int>();
+  r.bin_code = bin_code.data_ptr<double>();
+  r.quota = quota.data_ptr<int64_t>();
+  r.filled = filled.data_ptr<int64_t>();
+  r.seg_off = seg_off.data_ptr<int64_t>();
+  r.n_fixed = (int)nf;
+  r.fixed_j = nf ? fixed_j.data_ptr<int>() : nullptr;
+  r.fixed_code = nf ? fixed_code.data_ptr<double>() : nullptr;
+  r.stats = stats.data_ptr<int64_t>();
+  return r;
+}
+
+void cond_request(const Tensor& drive, const Tensor& bin_opt, const Tensor& bin_code, const Tensor& quota,
+                  const Tensor& filled, const Tensor& seg_off, const Tensor& fixed_j, const Tensor& fixed_code,
+                  const Tensor& stats, const Tensor& col, const Tensor& opt, const Tensor& tgt,
+                  const optional<Tensor>& h, int64_t cc, const Tensor& cond_off, const Tensor& cond_w, int64_t seed,
+                  const Tensor& rng_ctr, int64_t stream) {
+  fedtgan::CondRequestArgs a{};
+  a.req = cond_req(drive, bin_opt, bin_code, quota, filled, seg_off, fixed_j, fixed_code, stats);
+  a.rows = (int)tgt.numel();
+  for (const Tensor* t : {&col, &opt, &tgt})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() >= a.rows,
+                "cond_request: col / opt / tgt must be int32 with one entry per row");
+  TORCH_CHECK(cond_off.is_cuda() && cond_off.scalar_type() == at::kInt && cond_off.is_contiguous() &&
+                  cond_w.is_cuda() && cond_w.scalar_type() == at::kInt && cond_w.is_contiguous() &&
+                  cond_w.numel() == cond_off.numel() && cond_off.numel() >= 1, "cond_request: int32 span tables");
+  a.col = col.data_ptr<int>();
+  a.opt = opt.data_ptr<int>();
+  a.tgt = tgt.data_ptr<int>();
+  a.cond_off = cond_off.data_ptr<int>();
+  a.cond_w = cond_w.data_ptr<int>();
+  a.n_span = (int)cond_off.numel();
+  if (h.has_value() && h->defined()) {
+    check_f32_2d(*h, "cond_request h");
+    TORCH_CHECK(h->size(0) >= a.rows && cc >= 0 && cc < h->size(1), "cond_request: h rows / conditional block");
+    a.h = fp(*h);
+    a.ldh = ld_of(*h);
+    a.cc = (int)cc;
+    a.C = (int)(h->size(1) - cc);
+  }
+  a.seed = (uint64_t)seed;
+  a.rng_ctr = ctr_ptr(rng_ctr);
+  a.rng_stream = (uint32_t)stream;
+  fedtgan::launch_cond_request(a, cur_stream());
+}
+
+void cond_partition(const Tensor& drive, const Tensor& bin_opt, const Tensor& bin_code, const Tensor& quota,
+                    const Tensor& filled, const Tensor& seg_off, const Tensor& fixed_j, const Tensor& fixed_code,
+                    const Tensor& stats, const Tensor& out, const Tensor& tgt, const Tensor& dst, const Tensor& keep,
+                    const Tensor& counts) {
+  fedtgan::CondPartitionArgs a{};
+  a.req = cond_req(drive, bin_opt, bin_code, quota, filled, seg_off, fixed_j, fixed_code, stats);
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kDouble && out.is_contiguous() && out.dim() == 2,
+              "cond_partition: out must be contiguous float64 [rows, n_cols]");
+  TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == at::kDouble && dst.is_contiguous() && dst.dim() == 2 &&
+                  dst.size(1) == out.size(1), "cond_partition: dst must be contiguous float64 [n, n_cols]");
+  TORCH_CHECK(out.numel() < (int64_t)INT32_MAX, "cond_partition: a pass holds fewer than 2^31 values");
+  a.out = out.data_ptr<double>();
+  a.rows = (int)out.size(0);
+  a.n_cols = (int)out.size(1);
+  a.dst = dst.data_ptr<double>();
+  a.n_dst = dst.size(0);
+  const int64_t n_wg = fedtgan::cond_partition_workgroups(a.rows);
+  for (const Tensor* t : {&tgt, &keep, &counts})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous(), "cond_partition: int32 buffers");
+  TORCH_CHECK(tgt.numel() >= a.rows && keep.numel() >= a.rows && counts.numel() >= n_wg * a.req.n_bins,
+              "cond_partition: tgt / keep need one entry per row, counts one per workgroup and bin");
+  a.tgt = tgt.data_ptr<int>();
+  a.keep = keep.data_ptr<int>();
+  a.counts = counts.data_ptr<int>();
+  fedtgan::launch_cond_partition(a, cur_stream());
+}
+
+int64_t cond_partition_workgroups(int64_t rows) { return fedtgan::cond_partition_workgroups((int)rows); }
+
 // ----------------------------------------------------------------------------- native RCCL plane (csrc/comm)
 void rccl_load_op(const std::string& path) { fedtgan::comm::rccl_load(path); }
 
@@ -1230,7 +1324,8 @@ void vgm_fit(const Tensor& x, const Tensor& n_rows, const c10::optional<Tensor>&
 // checked build: the check bits raised by every kernel since the last call (cleared); synchronises
 int64_t check_status() {
   (void)hipDeviceSynchronize();
-  return (int64_t)(fedtgan::check_status_gemm() | fedtgan::check_status_ctgan_ops() | fedtgan::check_status_vgm());
+  return (int64_t)(fedtgan::check_status_gemm() | fedtgan::check_status_ctgan_ops() | fedtgan::check_status_vgm() |
+                   fedtgan::check_status_cond_gen());
 }
 
 #ifdef FEDTGAN_CHECKED
@@ -1463,6 +1558,15 @@ TORCH_LIBRARY(fedtgan, m) {
       "Tensor? ecol=None, Tensor? quads=None) -> ()");
   m.def("rng_bump(Tensor(a!) ctr) -> ()");
   m.def(
+      "cond_request(Tensor drive, Tensor bin_opt, Tensor bin_code, Tensor quota, Tensor filled, Tensor seg_off, "
+      "Tensor fixed_j, Tensor fixed_code, Tensor stats, Tensor(a!) col, Tensor(b!) opt, Tensor(c!) tgt, Tensor(d!)? h, "
+      "int cc, Tensor cond_off, Tensor cond_w, int seed, Tensor rng_ctr, int stream) -> ()");
+  m.def(
+      "cond_partition(Tensor drive, Tensor bin_opt, Tensor bin_code, Tensor quota, Tensor(a!) filled, Tensor seg_off, "
+      "Tensor fixed_j, Tensor fixed_code, Tensor(b!) stats, Tensor out, Tensor tgt, Tensor(c!) dst, Tensor(d!) keep, "
+      "Tensor(e!) counts) -> ()");
+  m.def("cond_partition_workgroups(int rows) -> int", &cond_partition_workgroups);
+  m.def(
       "vgm_estep(Tensor x, Tensor n_rows, Tensor consts, Tensor means, Tensor prec, Tensor(a!) partial, "
       "int rows_per_block) -> ()");
   m.def("kmeans_step(Tensor x, Tensor n_rows, Tensor centers, Tensor(a!) partial, int rows_per_block) -> ()");
@@ -1515,6 +1619,8 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("adam_cs", &adam_cs);
   m.impl("sample_decode", &sample_decode);
   m.impl("rng_bump", &rng_bump);
+  m.impl("cond_request", &cond_request);
+  m.impl("cond_partition", &cond_partition);
   m.impl("vgm_encode", &vgm_encode);
   m.impl("vgm_estep", &vgm_estep);
   m.impl("kmeans_step", &kmeans_step);

@@ -410,6 +410,52 @@ void launch_sample_decode(const DecodeArgs& a, hipStream_t stream);
 
 void launch_rng_bump(uint64_t* ctr, hipStream_t stream);
 
+// Conditional generation (kernels/cond_gen.hip): a request for rows with given category values, entirely in
+// device buffers, so one captured pass serves every request with the same numbers of bins and fixed columns.
+constexpr int COND_MAX_BINS = 64;   // requested values of the driving column
+struct CondReq {
+  const int* drive;          // [2]: the driving column's cond-span index, its output column
+  int n_bins;
+  const int* bin_opt;        // [n_bins] option index in the driving span
+  const double* bin_code;    // [n_bins] label code the decoded row must carry
+  const int64_t* quota;      // [n_bins] rows wanted
+  int64_t* filled;           // [n_bins] rows delivered so far
+  const int64_t* seg_off;    // [n_bins] exclusive prefix of the quotas: first dst row of the bin's segment
+  int n_fixed;
+  const int* fixed_j;        // [n_fixed] output columns of the other requested columns
+  const double* fixed_code;  // [n_fixed] their label codes
+  int64_t* stats;            // [2]: rows generated, rows that passed the predicate
+};
+struct CondRequestArgs {
+  CondReq req;
+  int rows;
+  int* col;                  // [rows] the sampler's draw, overwritten with the driving span
+  int* opt;                  // [rows] ... and the drawn bin's option
+  int* tgt;                  // [rows] the drawn bin (-1: every quota is full)
+  float* h;                  // nullable: fp32 activation buffer whose one-hot block [cc, cc + C) follows the draw
+  int ldh, cc, C;
+  const int* cond_off;       // [n_span]
+  const int* cond_w;         // [n_span]
+  int n_span;
+  uint64_t seed;
+  const uint64_t* rng_ctr;
+  uint32_t rng_stream;
+};
+void launch_cond_request(const CondRequestArgs& a, hipStream_t stream);
+struct CondPartitionArgs {
+  CondReq req;
+  const double* out;         // [rows, n_cols] decoded pass
+  int rows, n_cols;
+  const int* tgt;            // [rows]
+  int* keep;                 // [rows] scratch: the row's bin if it is kept, else -1
+  int* counts;               // [cond_partition_workgroups(rows), n_bins] scratch: kept rows per workgroup and bin
+  double* dst;               // [n_dst, n_cols] the quota segments
+  int64_t n_dst;
+};
+int cond_partition_workgroups(int rows);
+void launch_cond_partition(const CondPartitionArgs& a, hipStream_t stream);
+unsigned check_status_cond_gen();
+
 struct GenWeightJob {
   const float* w;   // fp32 weight, element (n, k) at w[n * ldw + k * skw] (skw = 1: [N, K] rows; ldw = 1: input-major storage)
   int N, ldw, skw, kd, C;

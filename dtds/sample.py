@@ -21,15 +21,27 @@ def main(argv=None):
     p.add_argument("-out", default=None, help="CSV path (default {name}_synthetic.csv)")
     p.add_argument("-backend", default="auto", choices=["auto", "hip", "torch"])
     p.add_argument("-seed", type=int, default=0)
+    p.add_argument("-where", action="append", default=[], metavar="COL=VALUE",
+                   help="only rows whose categorical column COL is VALUE (repeatable)")
+    p.add_argument("-where_json", default=None,
+                   help="the same as JSON; one column may map values to weights, e.g. "
+                        "'{\"class\": {\"back.\": 1, \"satan.\": 1}, \"protocol_type\": \"tcp\"}' (-n rows split by weight)")
+    p.add_argument("-max_passes", type=int, default=64, help="generation passes a conditional request may take")
     args = p.parse_args(argv)
     import torch
+    from fed_tgan_amd.models.conditional import parse_where
     from fed_tgan_amd.models.generator_io import load_generator
+    where = parse_where(args.where, args.where_json)
     dev = torch.device("cuda", 0) if (torch.cuda.is_available() and args.backend != "torch") else torch.device("cpu")
     gen = load_generator(args.model, dev, backend=args.backend, seed=args.seed)
     out = args.out or f"{gen.name}_synthetic.csv"
     t0 = time.time()
-    gen.write_csv(out, args.n)
-    print(f"{args.n} rows -> {out} ({time.time() - t0:.3f} s, {gen.engine.ops.name} on {dev})", flush=True)
+    gen.write_csv(out, args.n, where=where or None, max_passes=args.max_passes)
+    cond = ""
+    if where:
+        lc = gen.engine.last_conditional
+        cond = f", {lc['passes']} passes, {lc['kept']} of {lc['generated']} generated rows accepted"
+    print(f"{args.n} rows -> {out} ({time.time() - t0:.3f} s, {gen.engine.ops.name} on {dev}{cond})", flush=True)
     return out
 
 

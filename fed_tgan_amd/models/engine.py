@@ -242,6 +242,8 @@ class CTGANEngine:
         self._gen_graphs: Dict[int, tuple] = {}   # n -> (hipGraph, H, logits, out) of generate_decoded
         self._gen_split: Dict[int, tuple] = {}    # n -> (prep graph, body graph, H, logits, out, col, opt)
         self._gen_done = None                     # event: the last pipelined generation body has finished
+        self._cond_ent: Dict[tuple, dict] = {}    # (m, bins, fixed columns) -> buffers / hipGraph of a conditional pass
+        self.last_conditional = None              # generate_decoded_where: passes, rows generated / kept, filled counts
         self.graphs: Dict[int, object] = {}    # steps per graph -> captured hipGraph
         self.capture_mode = "global"   # "thread_local" when several engines capture from threads
         self.bn_batches = 0       # num_batches_tracked of every BN layer
@@ -647,6 +649,7 @@ class CTGANEngine:
         self._gen_bufs = None
         self._gen_graphs = {}
         self._gen_split = {}
+        self._cond_ent = {}
 
     # ================================================================= forward pieces
     def _kpad(self, H, a: int, W: torch.Tensor):
@@ -1254,6 +1257,7 @@ class CTGANEngine:
         self.graphs.clear()
         self._gen_graphs.clear()
         self._gen_split.clear()
+        self._cond_ent.clear()
         self._gen_done = None
 
     @property
@@ -1301,6 +1305,150 @@ class CTGANEngine:
         if hasattr(self.ops, "check"):
             self.ops.check()
         return out
+
+    # ------------------------------------------------------------------ conditional generation
+    @torch.no_grad()
+    def generate_decoded_where(self, n: int, request: dict, max_passes: int = 64, chunk: int | None = None,
+                               use_graph: bool | None = None) -> torch.Tensor:
+        """Exactly n decoded rows carrying the requested category values: [n, n_cols] float64 on the device, grouped
+        by the driving column's requested values in request order, in generation order (pass, then row) inside a
+        group.  ``request``: models/conditional.py build_request (its quotas sum to n).
+
+        One pass over m rows (``chunk``, default a size fitted to n, at most cfg.gen_chunk): sample_gen ->
+        cond_request (every row's condition becomes the driving column's value of a bin drawn in proportion to the
+        open quotas) -> eval generator -> sample_decode -> cond_partition (rows that carry every requested value move
+        into their bin's quota segment).  The request lives in device buffers, so on the HIP backend with
+        cfg.gen_graph the pass is captured once per (m, bins, fixed columns) and replayed; use_graph=False issues the
+        same launches eagerly, and both give bit-identical tables from equal engine states.  Passes are issued in
+        bursts that cannot overshoot (ceil(open quota / m) of them), with one readback of the filled counters per
+        burst; max_passes passes without every quota full raise ConditionalSamplingError (no partial table).
+        ``self.last_conditional`` records passes, rows generated, rows kept and the per-value counts."""
+        from .conditional import ConditionalSamplingError
+        if self.gen_tables is None:
+            raise RuntimeError("set_generation_tables() first")
+        n = int(n)
+        quotas = [int(q) for q in request["quotas"]]
+        if n != int(request["n"]) or sum(quotas) != n:
+            raise ValueError(f"the request was built for {request['n']} rows, not {n}")
+        n_cols = len(self.gen_tables["cols"])
+        nb, nf = len(quotas), int(request["fixed_j"].numel())
+        if nb > getattr(self.ops, "COND_MAX_BINS", 64):
+            raise ValueError(f"{nb} requested values; the kernels' bin limit is {self.ops.COND_MAX_BINS}")
+        if n == 0:
+            self.last_conditional = {"passes": 0, "generated": 0, "kept": 0, "filled": [0] * nb,
+                                     "values": list(request["values"])}
+            return torch.empty(0, n_cols, dtype=torch.float64, device=self.device)
+        if use_graph is None:
+            use_graph = self.device.type == "cuda" and self.cfg.gen_graph and self.ops.name == "hip"
+        if chunk is not None:
+            m = int(chunk)
+            if m < 1:
+                raise ValueError("chunk must be positive")
+        else:       # a power of two with a quarter of slack for rejected rows: few distinct sizes to capture
+            m = min(int(self.cfg.gen_chunk), max(1024, 1 << int(np.ceil(np.log2(max(1.25 * n, 1.0))))))
+        if self._gen_done is not None:    # a pipelined body may still read the shared weight copies
+            torch.cuda.current_stream(self.device).wait_event(self._gen_done)
+        ent = self._cond_entry(m, nb, nf, n)
+        for k in ("drive", "bin_opt", "bin_code", "quota", "seg_off", "fixed_j", "fixed_code"):
+            ent["req"][k].copy_(request[k])
+        ent["req"]["filled"].zero_()
+        ent["req"]["stats"].zero_()
+        if use_graph and ent.get("graph") is None:
+            self._capture_cond(ent, m)
+        passes, filled = 0, [0] * nb
+        while True:
+            open_rows = sum(q - f for q, f in zip(quotas, filled))
+            if open_rows <= 0:
+                break
+            if passes >= int(max_passes):
+                self.last_conditional = self._cond_report(ent, request, passes, filled)
+                if hasattr(self.ops, "check"):     # (a request pointing outside its tables fills nothing: say that)
+                    self.ops.check()
+                raise ConditionalSamplingError(
+                    f"{passes} passes of {m} rows filled {sum(filled)} of {n} requested rows "
+                    f"(per value: {dict(zip(map(str, request['values']), filled))})", filled, quotas, request["values"])
+            burst = max(1, min(-(-open_rows // m), int(max_passes) - passes))
+            for _ in range(burst):
+                if use_graph:
+                    ent["graph"].replay()
+                else:
+                    self._cond_pass(ent, m)
+            passes += burst
+            filled = [int(x) for x in ent["req"]["filled"].tolist()]     # the one readback per burst
+        out = ent["dst"][:n].clone()
+        self.last_conditional = self._cond_report(ent, request, passes, filled)
+        if hasattr(self.ops, "check"):
+            self.ops.check()
+        return out
+
+    def _cond_report(self, ent, request, passes, filled):
+        st = ent["req"]["stats"].tolist()
+        return {"passes": int(passes), "generated": int(st[0]), "kept": int(st[1]), "filled": list(filled),
+                "values": list(request["values"])}
+
+    def _cond_entry(self, m: int, nb: int, nf: int, n: int) -> dict:
+        """Static buffers of a conditional pass over m rows for requests of nb bins and nf fixed columns: the pass's
+        activations / logits / conditions / targets / decoded rows, the request buffers the launches read, and the
+        quota segments (grown, and the graph dropped, when a request asks for more rows)."""
+        key = (m, nb, nf)
+        ent = self._cond_ent.get(key)
+        dev = self.device
+        if ent is None:
+            H = self._gen_h16(m) if self.gen16 else _padded_rows(m, self.Hw, dev)
+            i32 = lambda k: torch.zeros(k, dtype=torch.int32, device=dev)      # noqa: E731
+            i64 = lambda k: torch.zeros(k, dtype=torch.int64, device=dev)      # noqa: E731
+            f64 = lambda k: torch.zeros(k, dtype=torch.float64, device=dev)    # noqa: E731
+            ent = {"H": H, "lg": _padded_rows(m, self.Dd, dev), "col": i32(m), "opt": i32(m), "tgt": i32(m),
+                   "out": torch.empty(m, len(self.gen_tables["cols"]), dtype=torch.float64, device=dev),
+                   "req": {"drive": i32(2), "bin_opt": i32(nb), "bin_code": f64(nb), "quota": i64(nb),
+                           "filled": i64(nb), "seg_off": i64(nb), "fixed_j": i32(nf), "fixed_code": f64(nf),
+                           "stats": i64(2)},
+                   "dst": None, "graph": None}
+            self._cond_ent[key] = ent
+        if ent["dst"] is None or ent["dst"].shape[0] < n:
+            if ent["graph"] is not None:
+                torch.cuda.synchronize(dev)
+            ent["graph"] = None
+            ent["dst"] = torch.empty(n, len(self.gen_tables["cols"]), dtype=torch.float64, device=dev)
+        return ent
+
+    def _cond_pass(self, ent: dict, m: int):
+        o, req = self.ops, ent["req"]
+        H, lg, col, opt, tgt = ent["H"], ent["lg"], ent["col"], ent["opt"], ent["tgt"]
+        w16 = self._gen_weights16() if self.gen16 else None
+        o.sample_gen(self.gen_cond, H, self.c_cols, self.z_cols, col_out=col, opt_out=opt, stream_id=21)
+        # (stream 24: the request's own Philox stream; 21-23 are the generation sampler's, activation's and decode's)
+        o.cond_request(req, col, opt, tgt, self.gen_cond, h=None if w16 is not None else H, c_col0=self.c_cols[0],
+                       stream_id=24)
+        if w16 is None:
+            self._g_forward(H, lg, training=False, nhat=False, cond=(col, opt, True))
+        else:
+            self._g_forward16(H, lg, w16, (col, opt))
+        o.sample_decode(lg, ent["out"], self.gen_tables, stream_id=23)
+        o.cond_partition(req, ent["out"], tgt, ent["dst"])
+
+    def _capture_cond(self, ent: dict, m: int):
+        """Capture one conditional pass (as _capture_gen).  The warm-up pass sizes every lazily built table and
+        scratch buffer; the RNG counter and the request's counters are put back after it, so a graph-replayed run
+        starts from the state an eager run starts from."""
+        from ..utils.devsync import CAPTURE_LOCK
+        req = ent["req"]
+        with CAPTURE_LOCK:
+            ctr0 = self.ops.ctr.clone()
+            s = torch.cuda.Stream(self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(s):
+                self._cond_pass(ent, m)
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            torch.cuda.synchronize(self.device)
+            self.ops.ctr.copy_(ctr0)
+            req["filled"].zero_()
+            req["stats"].zero_()
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode=self.capture_mode):
+                self._cond_pass(ent, m)
+        ent["graph"] = g
 
     # ------------------------------------------------------------------ pipelined generation
     def can_split_generation(self) -> bool:

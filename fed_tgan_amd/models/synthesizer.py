@@ -75,8 +75,15 @@ class CTGANSynthesizer(BaseSynthesizer):
                 print(f"EPOCH {i}:   loss_d:{ld:>6.2f}   loss_g:{lg:>6.2f}   time taken: {time.time() - t:.2f} sec")
         return self
 
-    def sample(self, n: int) -> np.ndarray:
-        """Decoded rows (continuous values and categorical labels as in ``transformer.inverse_transform``)."""
+    def sample(self, n: int, where=None, max_passes: int = 64) -> np.ndarray:
+        """Decoded rows (continuous values and categorical labels as in ``transformer.inverse_transform``).
+
+        where ({column index: category value | {category value: weight}}, raw values as in the training data; see
+        models/conditional.py): exactly n rows carrying those values, grouped by the weighted column's values."""
+        if where:
+            from .conditional import request_from_codes
+            req = request_from_codes(self.transformer, [(int(j), v) for j, v in where.items()], int(n), self.device)
+            return self.engine.generate_decoded_where(int(n), req, max_passes=max_passes).cpu().numpy()
         return self.engine.generate_decoded(n).cpu().numpy()
 
     def sample_encoded(self, n: int) -> np.ndarray:

@@ -569,3 +569,31 @@ class HipOps:
                              self._decode_quads(tabs, logits.shape[1]))
         self.L.rng_bump(ctr)
         return out
+
+    # ------------------------------------------------------------------ conditional generation
+    COND_MAX_BINS = 64     # kernels/launch.h COND_MAX_BINS
+
+    @staticmethod
+    def _cond_req(req):
+        return (req["drive"], req["bin_opt"], req["bin_code"], req["quota"], req["filled"], req["seg_off"],
+                req["fixed_j"], req["fixed_code"], req["stats"])
+
+    def cond_request(self, req, col, opt, tgt, cond, h=None, c_col0=0, stream_id=0, ctr=None):
+        """Same contract as TorchOps.cond_request (kernels/cond_gen.hip cond_request_kernel); the draw is keyed on
+        (seed, stream_id, step counter, row).  h: only the fp32 activation buffer (a bf16 one holds no one-hot)."""
+        self.L.cond_request(*self._cond_req(req), col, opt, tgt, h, int(c_col0), cond["cond_offset"],
+                            cond["cond_width"], self.seed, self.ctr if ctr is None else ctr, int(stream_id) * 16)
+
+    def cond_partition(self, req, out, tgt, dst):
+        """Same contract (and bit-identical results) as TorchOps.cond_partition: flag + count, rank + copy, finish."""
+        m, nb = int(out.shape[0]), int(req["quota"].numel())
+        key = ("cond", m, nb)
+        sc = self._dec.get(key)
+        if sc is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("cond_partition scratch must be sized before graph capture")
+            sc = (torch.empty(max(m, 1), dtype=torch.int32, device=self.device),
+                  torch.empty(max(1, int(self.L.cond_partition_workgroups(m)) * nb), dtype=torch.int32,
+                              device=self.device))
+            self._dec[key] = sc
+        self.L.cond_partition(*self._cond_req(req), out, tgt, dst, sc[0], sc[1])

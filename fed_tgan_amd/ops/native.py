@@ -23,7 +23,8 @@ LIB_PATH = os.environ.get("FEDTGAN_LIB") or LIB_PATH
 CHECK_NAMES = {0: "sampler CSR pick outside the row lists", 1: "sampler data row outside the training matrix",
                2: "sampler condition outside the span tables", 3: "decode code index outside the code table",
                4: "decode mode index >= K", 5: "one-hot gather index outside the conditional block",
-               6: "encode label outside the lookup table"}
+               6: "encode label outside the lookup table",
+               7: "conditional request index outside its tables"}
 
 _lock = threading.Lock()
 _loaded = None

@@ -344,3 +344,63 @@ class TorchOps:
                 k = (x - torch.log(-torch.log(u))).argmax(1)
                 out[:, j] = codes[k].double()
         return out
+
+    # ------------------------------------------------------------------ conditional generation
+    COND_MAX_BINS = 64     # the HIP kernels' bin limit; the same request runs on either backend
+
+    def cond_request(self, req, col, opt, tgt, cond, h=None, c_col0=0, stream_id=0):
+        """Replace the generation sampler's conditions by a request's (models/conditional.py).
+
+        req: dict of tensors -- drive int32 [2] (cond-span index, output column of the driving column), and per bin
+        bin_opt int32, bin_code f64, quota / filled / seg_off int64; fixed_j int32 / fixed_code f64 per other
+        requested column; stats int64 [2].  Row b draws bin t with probability remaining_t / sum(remaining)
+        (remaining = quota - filled) in integers -- r = floor(u * total), the first bin whose running sum exceeds r,
+        so a full bin is never drawn -- and gets col[b] = drive[0], opt[b] = bin_opt[t], tgt[b] = t.  h (fp32
+        activations whose one-hot block starts at column c_col0; cond = the span tables cond_offset / cond_width):
+        the row's hot element moves with it.  Every quota full: tgt = -1, col / opt / h untouched."""
+        m = tgt.shape[0]
+        rem = (req["quota"] - req["filled"]).clamp_min(0)
+        total = int(rem.sum())
+        if total <= 0:
+            tgt.fill_(-1)
+            return
+        u = torch.rand(m, dtype=torch.float64, device=tgt.device)
+        r = torch.floor(u * total).long().clamp_(max=total - 1)
+        t = torch.searchsorted(torch.cumsum(rem, 0), r, right=True).clamp_(max=rem.numel() - 1)
+        span = req["drive"][0].long()
+        o = req["bin_opt"].long()[t]
+        if h is not None:
+            rows = torch.arange(m, device=tgt.device)
+            off = cond["cond_offset"].long()
+            h[rows, c_col0 + off[col[:m].long()] + opt[:m].long()] = 0.0
+            h[rows, c_col0 + off[span] + o] = 1.0
+        col[:m] = span.to(col.dtype)
+        opt[:m] = o.to(opt.dtype)
+        tgt.copy_(t.to(tgt.dtype))
+
+    def cond_partition(self, req, out, tgt, dst):
+        """Move the rows of a decoded pass that carry every requested value into their bin's quota segment of dst.
+
+        Row r is kept iff tgt[r] >= 0, out[r, drive[1]] == bin_code[tgt[r]] and out[r, fixed_j[k]] == fixed_code[k]
+        for every k (exact float64 compares).  The kept rows of bin t, in row order, continue the bin's segment:
+        the i-th of them goes to dst[seg_off[t] + filled[t] + i] while that index stays below seg_off[t] + quota[t];
+        the rest are dropped.  Then filled[t] = min(quota[t], filled[t] + kept_t), stats[0] += rows and
+        stats[1] += kept rows (dropped ones included).  Nothing else of dst is written."""
+        m = out.shape[0]
+        t = tgt[:m].long()
+        nb = req["quota"].numel()
+        keep = (t >= 0) & (t < nb)
+        tc = t.clamp(0, nb - 1)
+        keep &= out[:, int(req["drive"][1])] == req["bin_code"][tc]
+        for j, code in zip(req["fixed_j"].tolist(), req["fixed_code"].tolist()):
+            keep &= out[:, int(j)] == code
+        for b in range(nb):
+            idx = torch.nonzero(keep & (t == b)).view(-1)
+            q, f = int(req["quota"][b]), int(req["filled"][b])
+            take = idx[:max(0, q - f)]
+            if take.numel():
+                s = int(req["seg_off"][b]) + f
+                dst[s:s + take.numel()] = out[take]
+            req["filled"][b] = min(q, f + int(idx.numel()))
+        req["stats"][0] += m
+        req["stats"][1] += int(keep.sum())
