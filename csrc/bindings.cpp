@@ -1114,6 +1114,100 @@ void cond_partition(const Tensor& drive, const Tensor& bin_opt, const Tensor& bi
 
 int64_t cond_partition_workgroups(int64_t rows) { return fedtgan::cond_partition_workgroups((int)rows); }
 
+// ----------------------------------------------------------------------------- similarity evaluator
+namespace {
+bool sim_i32(const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(); }
+bool sim_f64(const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kDouble && t.is_contiguous(); }
+}  // namespace
+
+void sim_prepare(const Tensor& values, const Tensor& kind, const Tensor& slot, const Tensor& vocab, const Tensor& keys,
+                 const Tensor& valid, const Tensor& counts) {
+  TORCH_CHECK(sim_f64(values) && values.dim() == 2 && values.size(1) >= 1,
+              "sim_prepare: values must be contiguous float64 [rows, n_cols]");
+  TORCH_CHECK(values.numel() < (int64_t)INT32_MAX, "sim_prepare: a table holds fewer than 2^31 values");
+  TORCH_CHECK(sim_i32(kind) && sim_i32(slot) && kind.numel() == values.size(1) && slot.numel() == values.size(1),
+              "sim_prepare: int32 kind / slot, one entry per column");
+  TORCH_CHECK(sim_f64(keys) && keys.dim() == 2 && keys.size(1) >= values.size(0) && sim_i32(valid) &&
+                  valid.numel() == keys.size(0), "sim_prepare: keys float64 [n_cont, >= rows], valid int32 [n_cont]");
+  TORCH_CHECK(sim_i32(counts) && counts.dim() == 2 && sim_i32(vocab) && vocab.numel() == counts.size(0),
+              "sim_prepare: counts int32 [n_cat, width], vocab int32 [n_cat]");
+  fedtgan::SimPrepareArgs a{};
+  a.values = values.data_ptr<double>();
+  a.rows = (int)values.size(0);
+  a.n_cols = (int)values.size(1);
+  a.kind = kind.data_ptr<int>();
+  a.slot = slot.data_ptr<int>();
+  a.n_cont = (int)keys.size(0);
+  a.n_cat = (int)counts.size(0);
+  a.vocab = a.n_cat ? vocab.data_ptr<int>() : nullptr;
+  a.keys = a.n_cont ? keys.data_ptr<double>() : nullptr;
+  a.ldk = keys.size(1);
+  a.valid = a.n_cont ? valid.data_ptr<int>() : nullptr;
+  a.counts = a.n_cat ? counts.data_ptr<int>() : nullptr;
+  a.ldc = (int)counts.size(1);
+  fedtgan::launch_sim_prepare(a, cur_stream());
+}
+
+void sim_sort(const Tensor& keys, const Tensor& tmp, int64_t n) {
+  TORCH_CHECK(sim_f64(keys) && keys.dim() == 2 && sim_f64(tmp) && tmp.dim() == 2 && tmp.size(0) == keys.size(0) &&
+                  tmp.size(1) == keys.size(1), "sim_sort: keys / tmp must be contiguous float64 of one shape");
+  TORCH_CHECK(n >= 0 && n <= keys.size(1) && n < (int64_t)INT32_MAX, "sim_sort: n outside the key rows");
+  if (keys.size(0) == 0 || n == 0) return;
+  fedtgan::launch_sim_sort(keys.data_ptr<double>(), tmp.data_ptr<double>(), (int)keys.size(0), keys.size(1), (int)n,
+                           cur_stream());
+}
+
+void sim_w1(const Tensor& real, const Tensor& n_real, const Tensor& fake, const Tensor& n_fake, int64_t max_fake,
+            const Tensor& part, const Tensor& out) {
+  TORCH_CHECK(sim_f64(real) && real.dim() == 2 && sim_f64(fake) && fake.dim() == 2 && fake.size(0) == real.size(0),
+              "sim_w1: real / fake must be contiguous float64 [n_cont, rows]");
+  const int64_t nc = real.size(0);
+  TORCH_CHECK(sim_i32(n_real) && n_real.numel() == nc && sim_i32(n_fake) && n_fake.numel() == nc,
+              "sim_w1: int32 value counts, one per column");
+  TORCH_CHECK(max_fake >= 0 && max_fake <= fake.size(1) && real.size(1) + max_fake < (int64_t)INT32_MAX,
+              "sim_w1: max_fake outside the fake rows");
+  TORCH_CHECK(sim_f64(out) && out.numel() == nc, "sim_w1: out float64 [n_cont]");
+  if (nc == 0) return;
+  const int64_t chunks = fedtgan::sim_w1_chunks(real.size(1) + max_fake);
+  TORCH_CHECK(sim_f64(part) && part.numel() >= nc * chunks, "sim_w1: part needs ", nc * chunks, " float64");
+  fedtgan::SimW1Args a{};
+  a.real = real.data_ptr<double>();
+  a.ldr = real.size(1);
+  a.n_real = n_real.data_ptr<int>();
+  a.fake = fake.data_ptr<double>();
+  a.ldf = fake.size(1);
+  a.n_fake = n_fake.data_ptr<int>();
+  a.n_cont = (int)nc;
+  a.max_real = (int)real.size(1);
+  a.max_fake = (int)max_fake;
+  a.part = part.data_ptr<double>();
+  a.out = out.data_ptr<double>();
+  fedtgan::launch_sim_w1(a, cur_stream());
+}
+
+void sim_jsd(const Tensor& real, const Tensor& fake, const Tensor& out) {
+  TORCH_CHECK(sim_i32(real) && real.dim() == 2 && sim_i32(fake) && fake.dim() == 2 && fake.size(0) == real.size(0) &&
+                  fake.size(1) == real.size(1), "sim_jsd: real / fake counts must be contiguous int32 of one shape");
+  TORCH_CHECK(sim_f64(out) && out.numel() == real.size(0), "sim_jsd: out float64 [n_cat]");
+  if (real.size(0) == 0) return;
+  fedtgan::SimJsdArgs a{};
+  a.real = real.data_ptr<int>();
+  a.fake = fake.data_ptr<int>();
+  a.ldc = (int)real.size(1);
+  a.n_cat = (int)real.size(0);
+  a.out = out.data_ptr<double>();
+  fedtgan::launch_sim_jsd(a, cur_stream());
+}
+
+void sim_mean(const Tensor& scores, int64_t n_cat, int64_t n_cont) {
+  TORCH_CHECK(sim_f64(scores) && n_cat >= 0 && n_cont >= 0 && scores.numel() == 2 + n_cat + n_cont,
+              "sim_mean: scores float64 [2 + n_cat + n_cont]");
+  fedtgan::launch_sim_mean(scores.data_ptr<double>(), (int)n_cat, (int)n_cont, cur_stream());
+}
+
+int64_t sim_sort_tile() { return fedtgan::SIM_SORT_TILE; }
+int64_t sim_w1_chunks(int64_t n) { return fedtgan::sim_w1_chunks(n); }
+
 // ----------------------------------------------------------------------------- native RCCL plane (csrc/comm)
 void rccl_load_op(const std::string& path) { fedtgan::comm::rccl_load(path); }
 
@@ -1325,7 +1419,7 @@ void vgm_fit(const Tensor& x, const Tensor& n_rows, const c10::optional<Tensor>&
 int64_t check_status() {
   (void)hipDeviceSynchronize();
   return (int64_t)(fedtgan::check_status_gemm() | fedtgan::check_status_ctgan_ops() | fedtgan::check_status_vgm() |
-                   fedtgan::check_status_cond_gen());
+                   fedtgan::check_status_cond_gen() | fedtgan::check_status_similarity());
 }
 
 #ifdef FEDTGAN_CHECKED
@@ -1567,6 +1661,17 @@ TORCH_LIBRARY(fedtgan, m) {
       "Tensor(e!) counts) -> ()");
   m.def("cond_partition_workgroups(int rows) -> int", &cond_partition_workgroups);
   m.def(
+      "sim_prepare(Tensor values, Tensor kind, Tensor slot, Tensor vocab, Tensor(a!) keys, Tensor(b!) valid, "
+      "Tensor(c!) counts) -> ()");
+  m.def("sim_sort(Tensor(a!) keys, Tensor(b!) tmp, int n) -> ()");
+  m.def(
+      "sim_w1(Tensor real, Tensor n_real, Tensor fake, Tensor n_fake, int max_fake, Tensor(a!) part, "
+      "Tensor(b!) out) -> ()");
+  m.def("sim_jsd(Tensor real, Tensor fake, Tensor(a!) out) -> ()");
+  m.def("sim_mean(Tensor(a!) scores, int n_cat, int n_cont) -> ()");
+  m.def("sim_sort_tile() -> int", &sim_sort_tile);
+  m.def("sim_w1_chunks(int n) -> int", &sim_w1_chunks);
+  m.def(
       "vgm_estep(Tensor x, Tensor n_rows, Tensor consts, Tensor means, Tensor prec, Tensor(a!) partial, "
       "int rows_per_block) -> ()");
   m.def("kmeans_step(Tensor x, Tensor n_rows, Tensor centers, Tensor(a!) partial, int rows_per_block) -> ()");
@@ -1621,6 +1726,11 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("rng_bump", &rng_bump);
   m.impl("cond_request", &cond_request);
   m.impl("cond_partition", &cond_partition);
+  m.impl("sim_prepare", &sim_prepare);
+  m.impl("sim_sort", &sim_sort);
+  m.impl("sim_w1", &sim_w1);
+  m.impl("sim_jsd", &sim_jsd);
+  m.impl("sim_mean", &sim_mean);
   m.impl("vgm_encode", &vgm_encode);
   m.impl("vgm_estep", &vgm_estep);
   m.impl("kmeans_step", &kmeans_step);

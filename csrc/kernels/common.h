@@ -29,6 +29,7 @@ enum CheckCode : unsigned {
   CHK_ONEHOT = 5,        // GEMM one-hot gather: condition index outside the block
   CHK_ENCODE_LUT = 6,    // encode: label lookup outside the table
   CHK_COND_REQUEST = 7,  // conditional generation: bin / span / option / column / segment row outside its table
+  CHK_SIM_CODE = 8,      // similarity evaluator: categorical code outside [0, vocab)
 };
 #ifdef FEDTGAN_CHECKED
 #define FT_CHECK(flag, cond, code)                                  \

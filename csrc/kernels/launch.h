@@ -456,6 +456,50 @@ int cond_partition_workgroups(int rows);
 void launch_cond_partition(const CondPartitionArgs& a, hipStream_t stream);
 unsigned check_status_cond_gen();
 
+// Similarity evaluator (kernels/similarity.hip): Avg_JSD / Avg_WD of a decoded table against a real one, on the
+// device.  Counting is in integers and every fp64 sum has a fixed order, so a table scores bit-identically on every
+// run; no launch allocates or waits on the host.
+constexpr int SIM_SORT_TILE = 2048;   // doubles per sorted LDS tile / merged output tile
+enum SimKind : int { SIM_PLAIN = 0, SIM_NONNEG = 1, SIM_CAT = 2 };
+struct SimPrepareArgs {
+  const double* values;   // [rows, n_cols] decoded table, row-major
+  int rows, n_cols;
+  const int* kind;        // [n_cols] SimKind
+  const int* slot;        // [n_cols] row of keys (continuous) / counts (categorical)
+  const int* vocab;       // [n_cat] codes of column slot s lie in [0, vocab[s])
+  double* keys;           // [n_cont, ldk] column-major keys; +inf where the CSV would carry no number
+  int64_t ldk;
+  int* valid;             // [n_cont] finite keys per column
+  int* counts;            // [n_cat, ldc] occurrences of each code
+  int ldc, n_cont, n_cat;
+};
+void launch_sim_prepare(const SimPrepareArgs& a, hipStream_t stream);
+// rows [0, n) of every segment keys[s * ld ...] ascending, in place; tmp: scratch of the same shape
+void launch_sim_sort(double* keys, double* tmp, int n_seg, int64_t ld, int n, hipStream_t stream);
+struct SimW1Args {
+  const double* real;     // [n_cont, ldr] ascending
+  int64_t ldr;
+  const int* n_real;      // [n_cont]
+  const double* fake;     // [n_cont, ldf] ascending, the valid values first
+  int64_t ldf;
+  const int* n_fake;      // [n_cont] valid fake values
+  int n_cont, max_real, max_fake;
+  double* part;           // [n_cont, sim_w1_chunks(max_real + max_fake)] scratch
+  double* out;            // [n_cont]
+};
+int sim_w1_chunks(int64_t n);
+void launch_sim_w1(const SimW1Args& a, hipStream_t stream);
+struct SimJsdArgs {
+  const int* real;        // [n_cat, ldc] counts of the real categories (slots past the vocabulary: real-only values)
+  const int* fake;        // [n_cat, ldc]
+  int ldc, n_cat;
+  double* out;            // [n_cat]
+};
+void launch_sim_jsd(const SimJsdArgs& a, hipStream_t stream);
+// scores = [avg_jsd, avg_wd, jsd x n_cat, wd x n_cont]: the two means from the per-column values behind them
+void launch_sim_mean(double* scores, int n_cat, int n_cont, hipStream_t stream);
+unsigned check_status_similarity();
+
 struct GenWeightJob {
   const float* w;   // fp32 weight, element (n, k) at w[n * ldw + k * skw] (skw = 1: [N, K] rows; ldw = 1: input-major storage)
   int N, ldw, skw, kd, C;

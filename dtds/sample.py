@@ -27,6 +27,8 @@ def main(argv=None):
                    help="the same as JSON; one column may map values to weights, e.g. "
                         "'{\"class\": {\"back.\": 1, \"satan.\": 1}, \"protocol_type\": \"tcp\"}' (-n rows split by weight)")
     p.add_argument("-max_passes", type=int, default=64, help="generation passes a conditional request may take")
+    p.add_argument("-score_against", default=None, metavar="REAL.csv",
+                   help="also print Avg_JSD / Avg_WD of the generated rows against this table, scored on the device")
     args = p.parse_args(argv)
     import torch
     from fed_tgan_amd.models.conditional import parse_where
@@ -36,12 +38,18 @@ def main(argv=None):
     gen = load_generator(args.model, dev, backend=args.backend, seed=args.seed)
     out = args.out or f"{gen.name}_synthetic.csv"
     t0 = time.time()
-    gen.write_csv(out, args.n, where=where or None, max_passes=args.max_passes)
+    scores = None
+    if args.score_against:
+        scores = gen.write_csv_scored(out, args.n, args.score_against, where=where or None, max_passes=args.max_passes)
+    else:
+        gen.write_csv(out, args.n, where=where or None, max_passes=args.max_passes)
     cond = ""
     if where:
         lc = gen.engine.last_conditional
         cond = f", {lc['passes']} passes, {lc['kept']} of {lc['generated']} generated rows accepted"
     print(f"{args.n} rows -> {out} ({time.time() - t0:.3f} s, {gen.engine.ops.name} on {dev}{cond})", flush=True)
+    if scores is not None:
+        print(f"Avg_JSD {scores[0]!r} Avg_WD {scores[1]!r} (against {args.score_against})", flush=True)
     return out
 
 

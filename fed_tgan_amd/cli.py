@@ -105,6 +105,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="generate round r's table on a side stream after a model snapshot (FedConfig.pipeline_sample)")
     p.add_argument("-table_reader", default="auto", choices=["auto", "pandas", "arrow"],
                    help="client CSV reader (pyarrow from 32 MiB up with auto)")
+    p.add_argument("-eval_every", type=int, default=0,
+                   help="score every N-th round's table on the device (Avg_JSD / Avg_WD -> the metrics log and "
+                        "{name}_result/similarity_online.csv); 0 = off")
+    p.add_argument("-eval_real", type=str, default=None,
+                   help="the real table's CSV for -eval_every (default: the clients' synthetic shards, rebuilt)")
     p.add_argument("-quiet", action="store_true")
     return p
 
@@ -138,7 +143,8 @@ def fed_config_from_args(args):
                      heartbeat_s=args.heartbeat,
                      dump_real=args.dump_real, async_csv=not args.sync_csv, init=args.init,
                      batched_clients=args.batched_clients, table_reader=args.table_reader,
-                     pipeline_sample={"auto": None, "on": True, "off": False}[args.pipeline_sample])
+                     pipeline_sample={"auto": None, "on": True, "off": False}[args.pipeline_sample],
+                     eval_every=args.eval_every, eval_real=args.eval_real)
 
 
 def pick_device(rank: int, colocated: bool, backend: str, mode: str = "fedavg") -> torch.device:
@@ -251,9 +257,18 @@ def free_port() -> int:
 
 
 def main(argv: Optional[List[str]] = None) -> None:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
     if args.world_size is None:
         args.world_size = 1 if args.local_clients else 2
+    if args.eval_every > 0 and not args.eval_real:
+        from .fed.runtime import eval_needs_real_table
+        if args.mode == "mdgan":
+            parser.error("-eval_every scores the FedAvg rounds' tables; the MD-GAN mode has none")
+        if eval_needs_real_table(fed_config_from_args(args), args.world_size * max(args.local_clients, 1),
+                                 args.world_size):
+            parser.error("-eval_every with -datapath needs -eval_real: the federator cannot rebuild tables the "
+                         "clients read from their own CSVs")
     if args.local_clients:
         if args.mode == "mdgan":
             raise SystemExit("-local_clients: the MD-GAN split mode runs one client per process")

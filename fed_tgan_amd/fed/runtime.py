@@ -35,7 +35,7 @@ import json
 import os
 import threading
 import time
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import pandas as pd
@@ -159,6 +159,20 @@ class FedConfig:
     # write models/label_encoders_{name}.pickle during initialisation (a helper process, as the reference writes it
     # there) instead of after the last round
     label_encoders_early: bool = True
+    # score every N-th round's table on the device (eval/device.py: Avg_JSD / Avg_WD against the real table) as it
+    # is generated; 0 = off, and the round then issues exactly what it issues without the feature.  eval_real: the
+    # real table's CSV; without it the clients' synthetic shards are rebuilt (clients that read their own CSVs
+    # need it).  The scores go to the metrics log and {name}_result/similarity_online.csv
+    eval_every: int = 0
+    eval_real: Optional[str] = None
+
+
+def eval_needs_real_table(cfg: FedConfig, n_clients: int, world_size: int) -> bool:
+    """eval_every without eval_real only works when every client's shard is synthetic: is a client CSV there?"""
+    if int(cfg.eval_every) <= 0 or cfg.eval_real or not cfg.datapath:
+        return False
+    return any(os.path.exists(cfg.datapath.format(client=i, rank=r))
+               for i in range(max(n_clients, 1)) for r in range(max(world_size, 1)))
 
 
 def _log(cfg: FedConfig, rank: int, *msg):
@@ -258,24 +272,110 @@ class FedRuntime:
     # ================================================================= data
     def _local_frame(self) -> pd.DataFrame:
         cfg, c = self.cfg, self.comm
-        k, idx = c.n_clients, c.client_index
+        idx = c.client_index
         if cfg.datapath:
             path = cfg.datapath.format(client=idx, rank=self.rank)
             if os.path.exists(path):
                 return read_csv_table(path, cfg.table_reader)
             print(f"[data] rank {self.rank}: {path} not found; using the synthetic {cfg.spec.name}-schema "
                   f"generator ({cfg.synthetic_rows} rows, shard mode {cfg.shard_mode})", flush=True)
-        if cfg.shard_mode == "independent":
-            df = generate(cfg.spec, cfg.synthetic_rows, seed=cfg.seed * 1000 + idx, as_category=True)
-        else:
-            full = generate(cfg.spec, cfg.synthetic_rows * k, seed=cfg.seed, as_category=True)
-            df = shard(full, k, cfg.shard_mode, seed=cfg.seed, target=cfg.spec.target_column,
-                       alpha=cfg.dirichlet_alpha)[idx]
+        df = self._synthetic_shards([idx])[0]
         if cfg.dump_real:
             d = os.path.join(cfg.out_dir, "data", "raw")
             os.makedirs(d, exist_ok=True)
             df.to_csv(os.path.join(d, f"{self.name}_train_client{idx}.csv"), index=False)
         return df
+
+    def _synthetic_shards(self, clients: Sequence[int]) -> List[pd.DataFrame]:
+        """The synthetic shards of the given clients (deterministic in the seed)."""
+        cfg, k = self.cfg, self.comm.n_clients
+        if cfg.shard_mode == "independent":
+            return [generate(cfg.spec, cfg.synthetic_rows, seed=cfg.seed * 1000 + i, as_category=True) for i in clients]
+        full = generate(cfg.spec, cfg.synthetic_rows * k, seed=cfg.seed, as_category=True)
+        parts = shard(full, k, cfg.shard_mode, seed=cfg.seed, target=cfg.spec.target_column, alpha=cfg.dirichlet_alpha)
+        return [parts[i] for i in clients]
+
+    # ================================================================= online similarity (FedConfig.eval_every)
+    def _eval_frame(self) -> pd.DataFrame:
+        """The real table the rounds are scored against: -eval_real, or the clients' synthetic shards rebuilt with
+        the generator calls _local_frame uses -- the table merge_real_shards would write, read back as a CSV."""
+        cfg = self.cfg
+        if cfg.eval_real:
+            return pd.read_csv(cfg.eval_real)
+        if eval_needs_real_table(cfg, self.comm.n_clients, self.comm.world_size):
+            raise ValueError("eval_every: the clients read their own CSVs; give the table to score against (eval_real)")
+        import io
+        buf = io.StringIO()
+        pd.concat(self._synthetic_shards(range(self.comm.n_clients))).to_csv(buf, index=False)
+        buf.seek(0)
+        return pd.read_csv(buf)
+
+    def _prepare_similarity(self):
+        """Federator: the device evaluator of the epoch tables, built and run once on a table of the real size
+        during initialisation (real columns sorted, code objects loaded, pinned result rows paged in)."""
+        cfg = self.cfg
+        self._sim = None
+        self._sim_pending: List[tuple] = []
+        self._sim_rows: List[tuple] = []
+        if not self.is_fed or int(cfg.eval_every) <= 0 or cfg.mode != "fedavg":
+            return
+        from ..eval.device import DeviceSimilarity
+        self._sim = DeviceSimilarity(self._eval_frame(), self.global_meta, self.vocabs, self.device,
+                                     ops=self.engine.ops, max_rows=self.n_sample)
+        cuda = self.device.type == "cuda"
+        self._sim_host = torch.zeros((max(int(cfg.epochs), 1), 2), dtype=torch.float64, pin_memory=cuda)
+        warm = torch.zeros((self.n_sample, len(self.global_meta["columns"])), dtype=torch.float64, device=self.device)
+        self._sim.score(warm)
+        if cuda:
+            self._sim_host[0].copy_(self._sim.scores[:2], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+
+    def _score_table(self, table, epoch: int):
+        """Score the round's table (every N-th round) where it first exists on the federator: queued on the current
+        stream -- the one that produced the rows -- ahead of the table's pinned copy; the two averages follow into
+        a pinned row behind an event, and nothing here waits for the device.  A table the gather delivered on the
+        host is uploaded first."""
+        sim = getattr(self, "_sim", None)
+        every = int(self.cfg.eval_every)
+        if sim is None or table is None or every <= 0 or (epoch + 1) % every:
+            return
+        t = table if torch.is_tensor(table) else torch.from_numpy(table)
+        if t.device != sim.keys.device:
+            t = t.to(sim.keys.device, non_blocking=True)
+        scores = sim.score(t)
+        if t.is_cuda:
+            row = self._sim_host[epoch % self._sim_host.shape[0]]
+            row.copy_(scores.buf[:2], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(t.device))
+        else:
+            row, ev = scores.buf[:2].clone(), None
+        self._sim_pending.append((epoch, row, ev))
+
+    def _collect_scores(self, wait: bool = False):
+        """Move the scores whose copy has landed (wait: all of them) to the metrics log and the run's table."""
+        pending = getattr(self, "_sim_pending", None)
+        while pending:
+            epoch, row, ev = pending[0]
+            if ev is not None:
+                if wait:
+                    ev.synchronize()
+                elif not ev.query():
+                    break
+            pending.pop(0)
+            jsd, wd = (float(x) for x in row.tolist())
+            self._sim_rows.append((epoch, jsd, wd))
+            if self.metrics is not None:
+                self.metrics.write({"epoch": epoch, "avg_jsd": jsd, "avg_wd": wd})
+
+    def write_similarity_online(self) -> Optional[str]:
+        """{name}_result/similarity_online.csv: the collected scores, with eval.similarity.similarity_table's columns."""
+        if getattr(self, "_sim", None) is None:
+            return None
+        self._collect_scores(wait=True)
+        path = os.path.join(self.result_dir(), "similarity_online.csv")
+        pd.DataFrame(self._sim_rows, columns=["Epoch_No.", "Avg_JSD", "Avg_WD"]).to_csv(path, index=False)
+        return path
 
     def merge_real_shards(self):
         """Federator: concatenate the clients' synthetic shards into data/raw/{name}_train.csv (for the
@@ -405,6 +505,7 @@ class FedRuntime:
             # threads): a failure falls back to per-thread engines instead of aborting round 0
             self._prepare_batched()
         self.csv_cols = csv_layout(merged, self.vocabs)     # None: a date format only the pandas path handles
+        self._prepare_similarity()      # (its uploads come before the barrier below, like every other one)
         if getattr(self, "thread_local_capture", False):
             # client threads of one process: none captures its graphs while another still uploads its tables (a
             # pageable host-to-device copy fails while any stream of the process captures -- with independent
@@ -768,6 +869,7 @@ class FedRuntime:
                 with self._sub("generate"):
                     vals = gen(per[0])
                 with self._sub("d2h"), on_gen():
+                    self._score_table(vals, epoch)
                     share = self._host(vals) if async_copy else vals.cpu().numpy()
         else:
             # every client decodes its share on its GPU; one gather to the federator (RCCL over
@@ -778,6 +880,7 @@ class FedRuntime:
                 rows = c.gather_rows(vals, per, samplers, dst=self.federator, to_host=not async_copy)
             with self._sub("d2h"), on_gen():
                 if self.is_fed:
+                    self._score_table(rows, epoch)
                     if rows.device.type == "cuda":
                         share = self._host(rows)
                     else:
@@ -827,10 +930,12 @@ class FedRuntime:
         with torch.cuda.stream(self._gen_stream):
             vals = self.engine.generation_body(k, self._gen_stream)
             if len(samplers) == 1 and not self._force_gather(samplers):
+                self._score_table(vals, epoch)
                 share = self._host(vals)
             else:
                 rows = self.comm.gather_rows(vals, per, samplers, dst=self.federator, to_host=False)
                 if self.is_fed:
+                    self._score_table(rows, epoch)
                     share = self._host(rows) if rows.device.type == "cuda" else rows.numpy()
         if self.is_fed and self.cfg.write_csv:
             self.write_epoch_csv(share, epoch)
@@ -859,6 +964,7 @@ class FedRuntime:
         self._complete_handoff()
         if self._writer is not None:
             self._writer.flush()
+        self._collect_scores(wait=True)
 
     def _write_epoch_csv(self, values, epoch: int):
         t0 = time.perf_counter()
@@ -1011,6 +1117,7 @@ class FedRuntime:
             if self.is_fed:
                 ld, lg = self.round_losses()
                 _log(cfg, self.rank, f"EPOCH {ep}: loss_d:{ld:>6.2f}   loss_g:{lg:>6.2f}   round time: {dt:.3f} sec")
+                self._collect_scores()      # earlier rounds' similarity scores whose copy has landed
                 if self.metrics is not None:
                     csv_t = self._csv_times.get(ep - 1)      # the previous table, written during this round
                     self.metrics.write({"epoch": ep, "round_s": dt, "loss_d": ld, "loss_g": lg,
@@ -1030,6 +1137,7 @@ class FedRuntime:
         if self.is_fed:
             self.write_label_encoders()
             self.write_timestamps()
+            self.write_similarity_online()
             if cfg.dump_real:
                 self.merge_real_shards()
             if cfg.save_generator:

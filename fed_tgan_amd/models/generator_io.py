@@ -58,6 +58,7 @@ class LoadedGenerator:
     transformer: VGMTransformer
     meta: dict
     vocabs: list
+    _similarity: dict = dataclasses.field(default_factory=dict, repr=False)   # (real table, n) -> its evaluator
 
     def sample(self, n: int, where=None, max_passes: int = 64) -> np.ndarray:
         """[n, n_columns] decoded values (label codes for categoricals), float64.  A GPU table comes
@@ -67,12 +68,10 @@ class LoadedGenerator:
         where ({column name: value | {value: weight}}, models/conditional.py): exactly n rows carrying the
         requested category values, grouped by the weighted column's values in request order; raises
         ConditionalSamplingError when max_passes generation passes do not fill the request."""
-        if where:
-            from .conditional import build_request
-            req = build_request(self.transformer, self.meta, self.vocabs, where, int(n), self.engine.device)
-            vals = self.engine.generate_decoded_where(int(n), req, max_passes=max_passes)
-        else:
-            vals = self.engine.generate_decoded(int(n))
+        return self._to_host(self.device_table(n, where=where, max_passes=max_passes))
+
+    @staticmethod
+    def _to_host(vals: torch.Tensor) -> np.ndarray:
         if not vals.is_cuda:
             return vals.numpy()
         host = torch.empty(vals.shape, dtype=vals.dtype, pin_memory=True)
@@ -82,6 +81,9 @@ class LoadedGenerator:
 
     def write_csv(self, path: str, n: int, threads: int = 0, where=None, max_passes: int = 64) -> str:
         vals = self.sample(n, where=where, max_passes=max_passes) if where else self.sample(n)
+        return self._write_values(path, vals, threads)
+
+    def _write_values(self, path: str, vals: np.ndarray, threads: int = 0) -> str:
         lay = csv_layout(self.meta, self.vocabs)
         if lay is not None:
             from ..utils import csvio
@@ -90,6 +92,40 @@ class LoadedGenerator:
                 return path
         decode_frame(vals, self.meta, self.vocabs).to_csv(path, index=False)
         return path
+
+    def score(self, real, n: int = 40000, where=None, max_passes: int = 64):
+        """(Avg_JSD, Avg_WD) of n generated rows against ``real`` (a DataFrame or a CSV path), as
+        ``eval.similarity.stat_sim`` gives them for the written CSV: generated and scored on the engine's device
+        (eval/device.py), only the two numbers come back.  The evaluator is kept per real table and n."""
+        return self._evaluator(real, n).score(self.device_table(n, where=where, max_passes=max_passes)).floats()
+
+    def write_csv_scored(self, path: str, n: int, real, threads: int = 0, where=None, max_passes: int = 64):
+        """:meth:`write_csv` and :meth:`score` of the same n rows: the table is scored on the device while it is
+        still there, then copied and written.  Returns (Avg_JSD, Avg_WD)."""
+        vals = self.device_table(n, where=where, max_passes=max_passes)
+        scores = self._evaluator(real, n).score(vals)
+        self._write_values(path, self._to_host(vals), threads)
+        return scores.floats()
+
+    def _evaluator(self, real, n: int):
+        import pandas as pd
+        from ..eval.device import DeviceSimilarity
+        key = (real if isinstance(real, str) else id(real), int(n))
+        if key not in self._similarity:
+            frame = pd.read_csv(real) if isinstance(real, str) else real
+            self._similarity.clear()
+            # (the frame is kept with its evaluator, so its id stays its own while the entry lives)
+            self._similarity[key] = (frame, DeviceSimilarity(frame, self.meta, self.vocabs, self.engine.device,
+                                                             ops=self.engine.ops, max_rows=int(n)))
+        return self._similarity[key][1]
+
+    def device_table(self, n: int, where=None, max_passes: int = 64) -> torch.Tensor:
+        """:meth:`sample`'s table where the engine left it: [n, n_columns] float64 on the engine's device"""
+        if where:
+            from .conditional import build_request
+            req = build_request(self.transformer, self.meta, self.vocabs, where, int(n), self.engine.device)
+            return self.engine.generate_decoded_where(int(n), req, max_passes=max_passes)
+        return self.engine.generate_decoded(int(n))
 
 
 def load_generator(path: str, device: Optional[torch.device] = None, backend: str = "auto",

@@ -597,3 +597,28 @@ class HipOps:
                               device=self.device))
             self._dec[key] = sc
         self.L.cond_partition(*self._cond_req(req), out, tgt, dst, sc[0], sc[1])
+
+    # ------------------------------------------------------------------ similarity evaluator
+    SIM_SORT_TILE = 2048   # kernels/launch.h SIM_SORT_TILE: keys per sorted LDS tile / merged output tile
+
+    def sim_prepare(self, values, kind, slot, vocab, keys, valid, counts):
+        """Same contract as TorchOps.sim_prepare (kernels/similarity.hip): one pass over the decoded table."""
+        self.L.sim_prepare(values, kind, slot, vocab, keys, valid, counts)
+
+    def sim_sort(self, keys, n, tmp):
+        """keys[:, :n] ascending per row, in place (LDS bitonic tiles + merge-path passes); tmp: same-shape scratch."""
+        self.L.sim_sort(keys, tmp, int(n))
+
+    @staticmethod
+    def sim_w1_part(n_cont: int, n: int) -> int:
+        """float64 scratch elements sim_w1 needs for n_cont columns of n real + fake values"""
+        return max(1, n_cont * int(native.require().sim_w1_chunks(int(n))))
+
+    def sim_w1(self, real, n_real, fake, n_fake, max_fake, out, part):
+        self.L.sim_w1(real, n_real, fake, n_fake, int(max_fake), part, out)
+
+    def sim_jsd(self, real_counts, fake_counts, out):
+        self.L.sim_jsd(real_counts, fake_counts, out)
+
+    def sim_mean(self, scores, n_cat, n_cont):
+        self.L.sim_mean(scores, int(n_cat), int(n_cont))

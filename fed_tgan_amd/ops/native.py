@@ -24,7 +24,8 @@ CHECK_NAMES = {0: "sampler CSR pick outside the row lists", 1: "sampler data row
                2: "sampler condition outside the span tables", 3: "decode code index outside the code table",
                4: "decode mode index >= K", 5: "one-hot gather index outside the conditional block",
                6: "encode label outside the lookup table",
-               7: "conditional request index outside its tables"}
+               7: "conditional request index outside its tables",
+               8: "similarity evaluator: categorical code outside its vocabulary"}
 
 _lock = threading.Lock()
 _loaded = None

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 EPI_NONE = 0
@@ -404,3 +405,92 @@ class TorchOps:
             req["filled"][b] = min(q, f + int(idx.numel()))
         req["stats"][0] += m
         req["stats"][1] += int(keep.sum())
+
+    # ------------------------------------------------------------------ similarity evaluator
+    SIM_SORT_TILE = 2048   # the HIP sort's tile; no meaning here beyond the shared attribute
+    SIM_PLAIN, SIM_NONNEG, SIM_CAT = 0, 1, 2
+
+    def sim_prepare(self, values, kind, slot, vocab, keys, valid, counts):
+        """One pass over a decoded table values [n, n_cols] float64 (eval/device.py DeviceSimilarity).
+
+        kind / slot int32 [n_cols]: a continuous column (SIM_PLAIN, or SIM_NONNEG = decoded by
+        data/decode.py nonneg_inverse first, where exactly -1 is the CSV's blank field) becomes row slot of keys
+        [n_cont, >= n] in the value space of the CSV, with +inf wherever the CSV carries no finite number, and
+        valid[slot] counts its finite values; a categorical column (SIM_CAT) counts its codes into counts[slot]
+        (int32 [n_cat, width]); codes outside [0, vocab[slot]) are ignored."""
+        n = values.shape[0]
+        counts.zero_()
+        valid.zero_()
+        width = counts.shape[1]
+        vl = vocab.tolist()
+        inf = float("inf")
+        for c, (k, s) in enumerate(zip(kind.tolist(), slot.tolist())):
+            col = values[:, c]
+            if k == self.SIM_CAT:
+                ok = (col >= 0) & (col < min(vl[s], width))
+                counts[s] += torch.bincount(col[ok].long(), minlength=width)[:width].to(counts.dtype)
+                continue
+            v = col.clone()
+            if k == self.SIM_NONNEG:
+                # the CSV's values come from numpy's exp (data/decode.py); on the CPU use the same one
+                e = torch.from_numpy(np.exp(v.numpy())) if v.device.type == "cpu" else torch.exp(v)
+                v = e - 1.0
+                v = torch.where(v < 0, torch.ceil(v), v)
+                v = torch.where(v == -1.0, torch.full_like(v, inf), v)
+            fin = torch.isfinite(v)
+            keys[s, :n] = torch.where(fin, v, torch.full_like(v, inf))
+            valid[s] = fin.sum()
+
+    def sim_sort(self, keys, n, tmp=None):
+        """keys[:, :n] ascending per row, in place."""
+        if n > 0 and keys.shape[0] > 0:
+            keys[:, :n] = torch.sort(keys[:, :n], dim=1).values
+
+    @staticmethod
+    def sim_w1_part(n_cont: int, n: int) -> int:
+        return 1
+
+    def sim_w1(self, real, n_real, fake, n_fake, max_fake, out, part=None):
+        """out[c] = W1 between the first n_real[c] values of real[c] and the first n_fake[c] of fake[c] (both
+        ascending), after the min-max scaling of the real values (scale 1 for a constant column): the integral of
+        |F_real - F_fake| as fed/stats.py wasserstein_1d computes it.  No real or no fake value: NaN."""
+        for c, (nr, m) in enumerate(zip(n_real.tolist(), n_fake.tolist())):
+            if nr <= 0 or m <= 0:
+                out[c] = float("nan")
+                continue
+            r, f = real[c, :nr], fake[c, :m]
+            lo, hi = r[0], r[-1]
+            scale = (hi - lo) if bool(hi > lo) else torch.ones_like(lo)
+            u, v = (r - lo) / scale, (f - lo) / scale
+            allv = torch.sort(torch.cat([u, v])).values
+            grid = allv[:-1].contiguous()
+            cu = torch.searchsorted(u.contiguous(), grid, right=True).double() / nr
+            cv = torch.searchsorted(v.contiguous(), grid, right=True).double() / m
+            out[c] = ((cu - cv).abs() * torch.diff(allv)).sum()
+
+    def sim_jsd(self, real_counts, fake_counts, out):
+        """out[c] = eval/similarity.py column_jsd from count vectors (int32 [n_cat, width]): frequencies over the
+        real categories (real count > 0); a real category with fake count 0 is appended a second time to both
+        vectors; other fake counts only enter the fake total; no real category in the fake column: 1."""
+        for c in range(real_counts.shape[0]):
+            r, f = real_counts[c].double(), fake_counts[c].double()
+            isr = real_counts[c] > 0
+            rp = r[isr] / r.sum()
+            ff = f[isr]
+            fv = torch.where(ff > 0, ff / f.sum().clamp_min(1.0), torch.zeros_like(ff))
+            miss = ff == 0
+            rv = torch.cat([rp, rp[miss]])
+            fv = torch.cat([fv, torch.zeros_like(rp[miss])])
+            if float(fv.sum()) == 0.0:
+                out[c] = 1.0
+                continue
+            p, q = rv / rv.sum(), fv / fv.sum()
+            mid = 0.5 * (p + q)
+            kl = lambda a: (a[a > 0] * torch.log(a[a > 0] / mid[a > 0])).sum()   # noqa: E731
+            js = 0.5 * (kl(p) + kl(q)) / math.log(2.0)
+            out[c] = torch.sqrt(js.clamp_min(0.0))
+
+    def sim_mean(self, scores, n_cat, n_cont):
+        """scores = [avg_jsd, avg_wd, jsd x n_cat, wd x n_cont]: the first two from the rest (NaN: no such column)."""
+        scores[0] = scores[2:2 + n_cat].mean() if n_cat else float("nan")
+        scores[1] = scores[2 + n_cat:2 + n_cat + n_cont].mean() if n_cont else float("nan")
