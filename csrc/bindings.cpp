@@ -1208,6 +1208,90 @@ void sim_mean(const Tensor& scores, int64_t n_cat, int64_t n_cont) {
 int64_t sim_sort_tile() { return fedtgan::SIM_SORT_TILE; }
 int64_t sim_w1_chunks(int64_t n) { return fedtgan::sim_w1_chunks(n); }
 
+// ----------------------------------------------------------------------------- privacy evaluator
+void nn_pack(const Tensor& values, const Tensor& kind, const Tensor& slot, const Tensor& lo, const Tensor& scale,
+             const Tensor& cont, const Tensor& cat) {
+  TORCH_CHECK(sim_f64(values) && values.dim() == 2 && values.size(1) >= 1,
+              "nn_pack: values must be contiguous float64 [rows, n_cols]");
+  TORCH_CHECK(values.numel() < (int64_t)INT32_MAX, "nn_pack: a table holds fewer than 2^31 values");
+  TORCH_CHECK(sim_i32(kind) && sim_i32(slot) && kind.numel() == values.size(1) && slot.numel() == values.size(1),
+              "nn_pack: int32 kind / slot, one entry per column");
+  TORCH_CHECK(sim_f64(cont) && cont.dim() == 2 && cont.size(0) >= values.size(0) && sim_i32(cat) && cat.dim() == 2 &&
+                  cat.size(0) >= values.size(0), "nn_pack: cont float64 [>= rows, n_cont], cat int32 [>= rows, n_cat]");
+  TORCH_CHECK(sim_f64(lo) && sim_f64(scale) && lo.numel() == cont.size(1) && scale.numel() == cont.size(1),
+              "nn_pack: lo / scale float64 [n_cont]");
+  fedtgan::NnPackArgs a{};
+  a.values = values.data_ptr<double>();
+  a.rows = (int)values.size(0);
+  a.n_cols = (int)values.size(1);
+  a.kind = kind.data_ptr<int>();
+  a.slot = slot.data_ptr<int>();
+  a.n_cont = (int)cont.size(1);
+  a.n_cat = (int)cat.size(1);
+  a.lo = a.n_cont ? lo.data_ptr<double>() : nullptr;
+  a.scale = a.n_cont ? scale.data_ptr<double>() : nullptr;
+  a.cont = a.n_cont ? cont.data_ptr<double>() : nullptr;
+  a.cat = a.n_cat ? cat.data_ptr<int>() : nullptr;
+  fedtgan::launch_nn_pack(a, cur_stream());
+}
+
+void nn_top2(const Tensor& q_cont, const Tensor& q_cat, const Tensor& r_cont, const Tensor& r_cat, bool exclude_self,
+             const Tensor& d1, const Tensor& d2, const Tensor& i1, const Tensor& scratch) {
+  TORCH_CHECK(sim_f64(q_cont) && q_cont.dim() == 2 && sim_i32(q_cat) && q_cat.dim() == 2 &&
+                  q_cat.size(0) == q_cont.size(0), "nn_top2: queries float64 [nq, n_cont] and int32 [nq, n_cat]");
+  TORCH_CHECK(sim_f64(r_cont) && r_cont.dim() == 2 && sim_i32(r_cat) && r_cat.dim() == 2 &&
+                  r_cat.size(0) == r_cont.size(0) && r_cont.size(1) == q_cont.size(1) &&
+                  r_cat.size(1) == q_cat.size(1), "nn_top2: reference rows with the queries' columns");
+  const int64_t nq = q_cont.size(0), nr = r_cont.size(0);
+  TORCH_CHECK(nr >= 1 && nr < (int64_t)INT32_MAX && nq < (int64_t)INT32_MAX && q_cont.size(1) + q_cat.size(1) >= 1,
+              "nn_top2: at least one reference row and one column");
+  TORCH_CHECK(!exclude_self || nq == nr, "nn_top2: exclude_self compares a table with itself");
+  TORCH_CHECK(sim_f64(d1) && sim_f64(d2) && sim_i32(i1) && d1.numel() >= nq && d2.numel() >= nq && i1.numel() >= nq,
+              "nn_top2: d1 / d2 float64 and i1 int32, one entry per query");
+  TORCH_CHECK(sim_f64(scratch) && scratch.numel() >= fedtgan::nn_scratch_doubles(nq, nr), "nn_top2: scratch needs ",
+              fedtgan::nn_scratch_doubles(nq, nr), " float64");
+  if (nq == 0) return;
+  fedtgan::NnTop2Args a{};
+  a.nq = (int)nq;
+  a.nr = (int)nr;
+  a.n_cont = (int)q_cont.size(1);
+  a.n_cat = (int)q_cat.size(1);
+  a.q_cont = a.n_cont ? q_cont.data_ptr<double>() : nullptr;
+  a.r_cont = a.n_cont ? r_cont.data_ptr<double>() : nullptr;
+  a.q_cat = a.n_cat ? q_cat.data_ptr<int>() : nullptr;
+  a.r_cat = a.n_cat ? r_cat.data_ptr<int>() : nullptr;
+  a.exclude_self = exclude_self ? 1 : 0;
+  fedtgan::launch_nn_top2(a, d1.data_ptr<double>(), d2.data_ptr<double>(), i1.data_ptr<int>(),
+                          scratch.data_ptr<double>(), cur_stream());
+}
+
+void nn_stats(const Tensor& d1, const Tensor& d2, int64_t n, const Tensor& keys, const Tensor& part) {
+  TORCH_CHECK(sim_f64(d1) && sim_f64(d2) && n >= 1 && n < (int64_t)INT32_MAX && d1.numel() >= n && d2.numel() >= n,
+              "nn_stats: d1 / d2 float64 with n >= 1 entries");
+  TORCH_CHECK(sim_f64(keys) && keys.dim() == 2 && keys.size(0) == 2 && keys.size(1) >= n,
+              "nn_stats: keys float64 [2, >= n]");
+  TORCH_CHECK(sim_f64(part) && part.numel() >= 2 * (int64_t)fedtgan::nn_stats_blocks(n), "nn_stats: part needs ",
+              2 * (int64_t)fedtgan::nn_stats_blocks(n), " float64");
+  fedtgan::launch_nn_stats(d1.data_ptr<double>(), d2.data_ptr<double>(), (int)n, keys.data_ptr<double>(), keys.size(1),
+                           part.data_ptr<double>(), cur_stream());
+}
+
+void nn_percentiles(const Tensor& keys, int64_t n, const Tensor& part, const Tensor& out) {
+  TORCH_CHECK(sim_f64(keys) && keys.dim() == 2 && keys.size(0) == 2 && n >= 1 && keys.size(1) >= n &&
+                  n < (int64_t)INT32_MAX, "nn_percentiles: keys float64 [2, >= n]");
+  TORCH_CHECK(sim_f64(part) && part.numel() >= 2 * (int64_t)fedtgan::nn_stats_blocks(n) && sim_f64(out) &&
+                  out.numel() >= 4, "nn_percentiles: part as nn_stats wrote it, out float64 [>= 4]");
+  fedtgan::launch_nn_percentiles(keys.data_ptr<double>(), keys.size(1), (int)n, part.data_ptr<double>(),
+                                 out.data_ptr<double>(), cur_stream());
+}
+
+int64_t nn_query_tile() { return fedtgan::NN_QUERY_TILE; }
+int64_t nn_ref_tile() { return fedtgan::NN_REF_TILE; }
+int64_t nn_chunk_rows() { return fedtgan::NN_CHUNK_ROWS; }
+int64_t nn_chunks(int64_t nr) { return fedtgan::nn_chunks(nr); }
+int64_t nn_scratch(int64_t nq, int64_t nr) { return fedtgan::nn_scratch_doubles(nq, nr); }
+int64_t nn_stats_part(int64_t n) { return 2 * (int64_t)fedtgan::nn_stats_blocks(n); }
+
 // ----------------------------------------------------------------------------- native RCCL plane (csrc/comm)
 void rccl_load_op(const std::string& path) { fedtgan::comm::rccl_load(path); }
 
@@ -1672,6 +1756,19 @@ TORCH_LIBRARY(fedtgan, m) {
   m.def("sim_sort_tile() -> int", &sim_sort_tile);
   m.def("sim_w1_chunks(int n) -> int", &sim_w1_chunks);
   m.def(
+      "nn_pack(Tensor values, Tensor kind, Tensor slot, Tensor lo, Tensor scale, Tensor(a!) cont, Tensor(b!) cat) -> ()");
+  m.def(
+      "nn_top2(Tensor q_cont, Tensor q_cat, Tensor r_cont, Tensor r_cat, bool exclude_self, Tensor(a!) d1, "
+      "Tensor(b!) d2, Tensor(c!) i1, Tensor(d!) scratch) -> ()");
+  m.def("nn_stats(Tensor d1, Tensor d2, int n, Tensor(a!) keys, Tensor(b!) part) -> ()");
+  m.def("nn_percentiles(Tensor keys, int n, Tensor part, Tensor(a!) out) -> ()");
+  m.def("nn_query_tile() -> int", &nn_query_tile);
+  m.def("nn_ref_tile() -> int", &nn_ref_tile);
+  m.def("nn_chunk_rows() -> int", &nn_chunk_rows);
+  m.def("nn_chunks(int nr) -> int", &nn_chunks);
+  m.def("nn_scratch(int nq, int nr) -> int", &nn_scratch);
+  m.def("nn_stats_part(int n) -> int", &nn_stats_part);
+  m.def(
       "vgm_estep(Tensor x, Tensor n_rows, Tensor consts, Tensor means, Tensor prec, Tensor(a!) partial, "
       "int rows_per_block) -> ()");
   m.def("kmeans_step(Tensor x, Tensor n_rows, Tensor centers, Tensor(a!) partial, int rows_per_block) -> ()");
@@ -1731,6 +1828,10 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("sim_w1", &sim_w1);
   m.impl("sim_jsd", &sim_jsd);
   m.impl("sim_mean", &sim_mean);
+  m.impl("nn_pack", &nn_pack);
+  m.impl("nn_top2", &nn_top2);
+  m.impl("nn_stats", &nn_stats);
+  m.impl("nn_percentiles", &nn_percentiles);
   m.impl("vgm_encode", &vgm_encode);
   m.impl("vgm_estep", &vgm_estep);
   m.impl("kmeans_step", &kmeans_step);

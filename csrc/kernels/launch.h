@@ -500,6 +500,49 @@ void launch_sim_jsd(const SimJsdArgs& a, hipStream_t stream);
 void launch_sim_mean(double* scores, int n_cat, int n_cont, hipStream_t stream);
 unsigned check_status_similarity();
 
+// Privacy evaluator (kernels/privacy.hip): distance to the closest record and nearest-neighbour distance ratio of a
+// decoded table against a real one.  d2(q, r) = sum over continuous columns of (q_c - r_c)^2 after the real table's
+// min-max scaling + the number of categorical columns whose codes differ, in fp64 from direct differences.
+constexpr int NN_QUERY_TILE = 256;    // query rows per workgroup (one per thread)
+constexpr int NN_REF_TILE = 16;       // reference rows staged in LDS at a time
+constexpr int NN_CHUNK_ROWS = 2048;   // reference rows per chunk (grid y); a (query, chunk) pair leaves one partial
+enum NnKind : int { NN_CONT = 0, NN_CAT = 1 };
+struct NnPackArgs {
+  const double* values;   // [rows, n_cols] decoded table, row-major
+  int rows, n_cols;
+  const int* kind;        // [n_cols] NnKind
+  const int* slot;        // [n_cols] column of cont / cat
+  const double* lo;       // [n_cont] the real column's minimum
+  const double* scale;    // [n_cont] 1 / (max - min), 1 for a constant column
+  double* cont;           // [rows, n_cont] (v - lo) * scale
+  int* cat;               // [rows, n_cat] codes (a value that is no code in [0, 2^31 - 1): -1)
+  int n_cont, n_cat;
+};
+void launch_nn_pack(const NnPackArgs& a, hipStream_t stream);
+struct NnTop2Args {
+  const double* q_cont;   // [nq, n_cont]
+  const int* q_cat;       // [nq, n_cat]
+  const double* r_cont;   // [nr, n_cont]
+  const int* r_cat;       // [nr, n_cat]
+  int nq, nr, n_cont, n_cat;
+  int exclude_self;       // reference row j == query row i is no candidate
+  int chunks;             // set by the launcher, as the partials are: [chunks, nq] each, carved from scratch
+  double* part_d1;
+  double* part_d2;
+  int* part_i1;
+};
+int nn_chunks(int64_t nr);
+int64_t nn_scratch_doubles(int64_t nq, int64_t nr);   // fp64 elements of scratch launch_nn_top2 needs
+// per query: d1 <= d2 the two smallest d2 over the candidates (with multiplicity; +inf where there are fewer) and
+// i1 the lowest index at distance d1 (-1: no candidate)
+void launch_nn_top2(NnTop2Args a, double* d1, double* d2, int* i1, double* scratch, hipStream_t stream);
+int nn_stats_blocks(int64_t n);
+// keys [2, ld]: sqrt(d1) and the ratio sqrt(d1 / d2) of rows [0, n); part [2 * nn_stats_blocks(n)]
+void launch_nn_stats(const double* d1, const double* d2, int n, double* keys, int64_t ld, double* part,
+                     hipStream_t stream);
+// out[0..3] = 5th percentile of each (ascending) key row, smallest sqrt(d1), share of rows with d1 == 0
+void launch_nn_percentiles(const double* keys, int64_t ld, int n, const double* part, double* out, hipStream_t stream);
+
 struct GenWeightJob {
   const float* w;   // fp32 weight, element (n, k) at w[n * ldw + k * skw] (skw = 1: [N, K] rows; ldw = 1: input-major storage)
   int N, ldw, skw, kd, C;

@@ -1,0 +1,319 @@
+// Privacy evaluator (eval/privacy.py DevicePrivacy): DCR / NNDR of a decoded table against a real one, on the device.
+//
+//  nn_pack_kernel         one pass over a row-major decoded table: continuous columns scaled by the real table's
+//                         min-max into a dense fp64 [n, n_cont] buffer, categorical codes into an int32 [n, n_cat] one
+//  nn_top2_kernel         all pairs, grid = (query tiles, reference chunks): a thread owns one query row (held in
+//                         registers), the workgroup shares a tile of NN_REF_TILE reference rows staged in LDS, and every
+//                         (query, chunk) pair leaves its partial (d1, d2, i1) in scratch
+//  nn_merge_kernel        the partials of a query folded in chunk order (strict <: the lowest index wins a tie)
+//  nn_stats_kernel        sqrt(d1) and the distance ratio into two key rows (sorted by launch_sim_sort afterwards);
+//                         per-workgroup minimum and count of exact zeros in fixed slots
+//  nn_percentile_kernel   the two interpolated 5th percentiles from the sorted rows, the minimum and the share of zeros
+//
+// d2(q, r) = sum over continuous columns of (q_c - r_c)^2, in column order, plus the number of categorical columns
+// whose codes differ, all in fp64 from direct differences: a copied record is at exactly 0.  Codes are compared, never
+// used as an index.  Every query's candidates are visited in ascending index order and partials meet in chunk order,
+// so a table scores bit-identically on every run; nothing is allocated and the host reads nothing back.
+#include "common.h"
+#include "launch.h"
+
+#include <math.h>
+#include <stdexcept>
+
+namespace fedtgan {
+
+constexpr int NN_THREADS = NN_QUERY_TILE;   // one query row per thread
+constexpr int NN_QC = 24;                   // continuous columns of a query held in registers at a time
+constexpr int NN_QK = 24;                   // categorical columns
+constexpr int NN_PAD_C = NN_REF_TILE + 2;   // LDS rows padded, still 16-B aligned for the wide broadcast reads
+constexpr int NN_PAD_K = NN_REF_TILE + 4;
+
+__device__ __forceinline__ double nn_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
+
+// ============================================================================ pack
+// one thread per cell: the table is read coalesced.  (v - lo) * scale is a subtraction and then a product: there is
+// no multiply-add in it for the compiler to contract, so the values equal the reference ops' bit for bit.
+__global__ __launch_bounds__(NN_THREADS) void nn_pack_kernel(NnPackArgs a) {
+  const long long i = (long long)blockIdx.x * NN_THREADS + threadIdx.x;
+  if (i >= (long long)a.rows * a.n_cols) return;
+  const long long r = i / a.n_cols;
+  const int c = (int)(i - r * a.n_cols);
+  const int k = a.kind[c], s = a.slot[c];
+  const double v = a.values[i];
+  if (k == NN_CAT) {
+    // (a NaN or out-of-range value is no code at all: -1 equals no code of either table's valid range)
+    if (s >= 0 && s < a.n_cat) a.cat[r * a.n_cat + s] = (v >= 0.0 && v < 2147483647.0) ? (int)v : -1;
+  } else if (s >= 0 && s < a.n_cont) {
+    a.cont[r * a.n_cont + s] = (v - a.lo[s]) * a.scale[s];
+  }
+}
+
+void launch_nn_pack(const NnPackArgs& a, hipStream_t stream) {
+  require_unbatched("nn_pack");
+  if (a.rows < 0 || a.n_cols <= 0 || a.n_cont < 0 || a.n_cat < 0) throw std::runtime_error("nn_pack: table sizes");
+  const long long cells = (long long)a.rows * a.n_cols;
+  if (cells == 0) return;
+  if (cells >= (long long)INT32_MAX * NN_THREADS) throw std::runtime_error("nn_pack: table too large");
+  hipLaunchKernelGGL(nn_pack_kernel, dim3((unsigned)((cells + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS), 0,
+                     stream, a);
+}
+
+// ============================================================================ all-pairs top-2
+// Columns are processed in blocks of NN_QC continuous + NN_QK categorical columns (block b holds continuous columns
+// [b NN_QC, ...) and categorical columns [b NN_QK, ...)); a table of up to 24 + 24 columns is one block and its query
+// row is loaded once.  Wider rows reload the query block per tile, and the per-thread accumulators of the tile's
+// NN_REF_TILE reference rows carry the partial sums across the blocks, so the continuous terms still add up in column
+// order; the mismatch count is an integer and joins at the end.
+//
+// The reference tile sits in LDS column-major ([column][row]): all lanes of a wave read the same address (a
+// broadcast, no bank conflict) and a column's 16 rows are contiguous for 16-byte reads.  The chunk is blockIdx.y, the
+// slow grid dimension: workgroups are dealt round-robin over the XCDs by linear id, so at any time every XCD works
+// on the same one or two chunks (0.5 MB each at 42 columns) and re-reads them from its own L2.
+__global__ __launch_bounds__(NN_THREADS) void nn_top2_kernel(NnTop2Args a) {
+  __shared__ __attribute__((aligned(16))) double sc[NN_QC][NN_PAD_C];
+  __shared__ __attribute__((aligned(16))) int sk[NN_QK][NN_PAD_K];
+  const int tid = threadIdx.x;
+  const int q = blockIdx.x * NN_QUERY_TILE + tid;
+  const bool live = q < a.nq;
+  const int chunk = blockIdx.y;
+  const int j0 = chunk * NN_CHUNK_ROWS;
+  const int j1 = min(a.nr, j0 + NN_CHUNK_ROWS);
+  const int nbc = (a.n_cont + NN_QC - 1) / NN_QC, nbk = (a.n_cat + NN_QK - 1) / NN_QK;
+  const int nblk = max(max(nbc, nbk), 1);
+  const double* qc = a.q_cont + (size_t)(live ? q : 0) * a.n_cont;
+  const int* qk = a.q_cat + (size_t)(live ? q : 0) * a.n_cat;
+
+  double qv[NN_QC];
+  int qi[NN_QK];
+  auto load_query = [&](int b) {
+#pragma unroll
+    for (int c = 0; c < NN_QC; ++c) {
+      const int col = b * NN_QC + c;
+      qv[c] = col < a.n_cont ? qc[col] : 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < NN_QK; ++c) {
+      const int col = b * NN_QK + c;
+      qi[c] = col < a.n_cat ? qk[col] : 0;
+    }
+  };
+  load_query(0);
+
+  double d1 = nn_inf(), d2 = nn_inf();
+  int i1 = -1;
+  for (int jt = j0; jt < j1; jt += NN_REF_TILE) {
+    double acc[NN_REF_TILE];
+    int cnt[NN_REF_TILE];
+#pragma unroll
+    for (int r = 0; r < NN_REF_TILE; ++r) {
+      acc[r] = 0.0;
+      cnt[r] = 0;
+    }
+    for (int b = 0; b < nblk; ++b) {
+      const int ncb = min(NN_QC, a.n_cont - b * NN_QC);     // columns of this block (<= 0: none)
+      const int nkb = min(NN_QK, a.n_cat - b * NN_QK);
+      __syncthreads();                                      // the previous tile / block has been consumed
+      if (nblk > 1) load_query(b);
+      for (int e = tid; e < NN_REF_TILE * NN_QC; e += NN_THREADS) {
+        const int r = e / NN_QC, c = e - r * NN_QC;
+        const int j = jt + r, col = b * NN_QC + c;
+        sc[c][r] = (j < j1 && col < a.n_cont) ? a.r_cont[(size_t)j * a.n_cont + col] : 0.0;
+      }
+      for (int e = tid; e < NN_REF_TILE * NN_QK; e += NN_THREADS) {
+        const int r = e / NN_QK, c = e - r * NN_QK;
+        const int j = jt + r, col = b * NN_QK + c;
+        sk[c][r] = (j < j1 && col < a.n_cat) ? a.r_cat[(size_t)j * a.n_cat + col] : 0;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int c = 0; c < NN_QC; ++c) {
+        if (c < ncb) {                                      // (uniform over the workgroup)
+          const double x = qv[c];
+#pragma unroll
+          for (int r = 0; r < NN_REF_TILE; ++r) {
+            const double d = x - sc[c][r];
+            acc[r] += d * d;
+          }
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < NN_QK; ++c) {
+        if (c < nkb) {
+          const int x = qi[c];
+#pragma unroll
+          for (int r = 0; r < NN_REF_TILE; ++r) cnt[r] += (x != sk[c][r]) ? 1 : 0;
+        }
+      }
+    }
+    // candidates in ascending index order; strict <, so the first of equal distances keeps i1 and the second
+    // becomes d2 (multiplicity)
+#pragma unroll
+    for (int r = 0; r < NN_REF_TILE; ++r) {
+      const int j = jt + r;
+      const bool ok = j < j1 && !(a.exclude_self && j == q);
+      const double d = ok ? acc[r] + (double)cnt[r] : nn_inf();
+      if (d < d1) {
+        d2 = d1;
+        d1 = d;
+        i1 = j;
+      } else if (d < d2) {
+        d2 = d;
+      }
+    }
+  }
+  if (live) {
+    const size_t o = (size_t)chunk * a.nq + q;
+    a.part_d1[o] = d1;
+    a.part_d2[o] = d2;
+    a.part_i1[o] = i1;
+  }
+}
+
+__global__ __launch_bounds__(NN_THREADS) void nn_merge_kernel(NnTop2Args a, double* out_d1, double* out_d2,
+                                                              int* out_i1) {
+  const int q = blockIdx.x * NN_THREADS + threadIdx.x;
+  if (q >= a.nq) return;
+  double d1 = nn_inf(), d2 = nn_inf();
+  int i1 = -1;
+  for (int c = 0; c < a.chunks; ++c) {          // chunk c holds indices below chunk c + 1's
+    const size_t o = (size_t)c * a.nq + q;
+    const double b1 = a.part_d1[o], b2 = a.part_d2[o];
+    if (b1 < d1) {
+      d2 = b2 < d1 ? b2 : d1;
+      d1 = b1;
+      i1 = a.part_i1[o];
+    } else if (b1 < d2) {
+      d2 = b1;
+    }
+  }
+  out_d1[q] = d1;
+  out_d2[q] = d2;
+  out_i1[q] = i1;
+}
+
+int nn_chunks(int64_t nr) {
+  const int64_t c = (nr + NN_CHUNK_ROWS - 1) / NN_CHUNK_ROWS;
+  return c > 0 ? (int)c : 1;
+}
+
+int64_t nn_scratch_doubles(int64_t nq, int64_t nr) {
+  const int64_t slots = nq * nn_chunks(nr);
+  const int64_t n = 2 * slots + (slots + 1) / 2;     // d1, d2, and i1 as int32
+  return n > 0 ? n : 1;
+}
+
+void launch_nn_top2(NnTop2Args a, double* d1, double* d2, int* i1, double* scratch, hipStream_t stream) {
+  require_unbatched("nn_top2");
+  if (a.nq < 0 || a.nr < 1 || a.n_cont < 0 || a.n_cat < 0 || a.n_cont + a.n_cat < 1)
+    throw std::runtime_error("nn_top2: table sizes");
+  if (a.nq == 0) return;
+  a.chunks = nn_chunks(a.nr);
+  if (a.chunks > 65535) throw std::runtime_error("nn_top2: too many reference rows");
+  const size_t slots = (size_t)a.nq * a.chunks;
+  a.part_d1 = scratch;
+  a.part_d2 = scratch + slots;
+  a.part_i1 = (int*)(scratch + 2 * slots);
+  const unsigned tiles = (unsigned)((a.nq + NN_QUERY_TILE - 1) / NN_QUERY_TILE);
+  hipLaunchKernelGGL(nn_top2_kernel, dim3(tiles, (unsigned)a.chunks), dim3(NN_THREADS), 0, stream, a);
+  hipLaunchKernelGGL(nn_merge_kernel, dim3(tiles), dim3(NN_THREADS), 0, stream, a, d1, d2, i1);
+}
+
+// ============================================================================ table scores
+// keys row 0: DCR = sqrt(d1); row 1: NNDR = sqrt(d1 / d2), 1 where d2 == 0, 0 where d2 = +inf.
+// part[b] = the workgroup's smallest DCR, part[blocks + b] = its count of d1 == 0 (an integer, exact as fp64)
+__global__ __launch_bounds__(NN_THREADS) void nn_stats_kernel(const double* d1, const double* d2, int n, double* keys,
+                                                              int64_t ld, double* part, int blocks) {
+  __shared__ double smin[NN_THREADS];
+  __shared__ int scnt[NN_THREADS];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * NN_THREADS + tid;
+  double dcr = nn_inf();
+  int zero = 0;
+  if (i < n) {
+    const double a = d1[i], b = d2[i];
+    dcr = sqrt(a);
+    keys[i] = dcr;
+    keys[ld + i] = b == 0.0 ? 1.0 : (isinf(b) ? 0.0 : sqrt(a / b));
+    zero = a == 0.0 ? 1 : 0;
+  }
+  smin[tid] = dcr;
+  scnt[tid] = zero;
+  __syncthreads();
+  for (int s = NN_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      smin[tid] = fmin(smin[tid], smin[tid + s]);
+      scnt[tid] += scnt[tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    part[blockIdx.x] = smin[0];
+    part[blocks + blockIdx.x] = (double)scnt[0];
+  }
+}
+
+// numpy's linear interpolation (function_base.py _lerp) at virtual index q (n - 1) of an ascending row
+__device__ __forceinline__ double nn_percentile(const double* x, int n, double q) {
+  const double pos = (double)(n - 1) * q;
+  int lo = (int)floor(pos);
+  lo = min(max(lo, 0), n - 1);
+  const int hi = min(lo + 1, n - 1);
+  const double t = pos - (double)lo;
+  const double u = x[lo], v = x[hi];
+  if (u == v || t == 0.0) return u;       // (also keeps an infinite neighbour out of an exact position)
+  const double diff = v - u;
+  return t >= 0.5 ? v - diff * (1.0 - t) : u + diff * t;
+}
+
+__global__ __launch_bounds__(NN_THREADS) void nn_percentile_kernel(const double* keys, int64_t ld, int n,
+                                                                   const double* part, int blocks, double* out) {
+  __shared__ double smin[NN_THREADS];
+  __shared__ long long scnt[NN_THREADS];
+  const int tid = threadIdx.x;
+  double m = nn_inf();
+  long long z = 0;
+  for (int b = tid; b < blocks; b += NN_THREADS) {
+    m = fmin(m, part[b]);
+    z += (long long)part[blocks + b];
+  }
+  smin[tid] = m;
+  scnt[tid] = z;
+  __syncthreads();
+  for (int s = NN_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      smin[tid] = fmin(smin[tid], smin[tid + s]);
+      scnt[tid] += scnt[tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    out[0] = nn_percentile(keys, n, 0.05);
+    out[1] = nn_percentile(keys + ld, n, 0.05);
+    out[2] = smin[0];
+    out[3] = (double)scnt[0] / (double)n;
+  }
+}
+
+int nn_stats_blocks(int64_t n) {
+  const int64_t b = (n + NN_THREADS - 1) / NN_THREADS;
+  return b > 0 ? (int)b : 1;
+}
+
+void launch_nn_stats(const double* d1, const double* d2, int n, double* keys, int64_t ld, double* part,
+                     hipStream_t stream) {
+  require_unbatched("nn_stats");
+  if (n < 1 || ld < n) throw std::runtime_error("nn_stats: row count / key row length");
+  const int blocks = nn_stats_blocks(n);
+  hipLaunchKernelGGL(nn_stats_kernel, dim3((unsigned)blocks), dim3(NN_THREADS), 0, stream, d1, d2, n, keys, ld, part,
+                     blocks);
+}
+
+void launch_nn_percentiles(const double* keys, int64_t ld, int n, const double* part, double* out,
+                           hipStream_t stream) {
+  require_unbatched("nn_percentiles");
+  if (n < 1 || ld < n) throw std::runtime_error("nn_percentiles: row count / key row length");
+  hipLaunchKernelGGL(nn_percentile_kernel, dim3(1), dim3(NN_THREADS), 0, stream, keys, ld, n, part,
+                     nn_stats_blocks(n), out);
+}
+
+}  // namespace fedtgan

@@ -7,6 +7,7 @@ The federator writes ``models/{name}_generator.pt`` after the last round (see
 (`Server/dtds/distributed.py:560-563`).
 """
 import argparse
+import json
 import os
 import sys
 import time
@@ -29,6 +30,9 @@ def main(argv=None):
     p.add_argument("-max_passes", type=int, default=64, help="generation passes a conditional request may take")
     p.add_argument("-score_against", default=None, metavar="REAL.csv",
                    help="also print Avg_JSD / Avg_WD of the generated rows against this table, scored on the device")
+    p.add_argument("-privacy_against", default=None, metavar="REAL.csv",
+                   help="also print one JSON line with DCR / NNDR of the generated rows against this table (5th "
+                        "percentiles, minimum, share of exact copies, and the real table's own baseline)")
     args = p.parse_args(argv)
     import torch
     from fed_tgan_amd.models.conditional import parse_where
@@ -38,9 +42,11 @@ def main(argv=None):
     gen = load_generator(args.model, dev, backend=args.backend, seed=args.seed)
     out = args.out or f"{gen.name}_synthetic.csv"
     t0 = time.time()
-    scores = None
-    if args.score_against:
-        scores = gen.write_csv_scored(out, args.n, args.score_against, where=where or None, max_passes=args.max_passes)
+    scores = privacy = None
+    if args.score_against or args.privacy_against:
+        scores, privacy = gen.write_csv_evaluated(out, args.n, score_real=args.score_against,
+                                                  privacy_real=args.privacy_against, where=where or None,
+                                                  max_passes=args.max_passes)
     else:
         gen.write_csv(out, args.n, where=where or None, max_passes=args.max_passes)
     cond = ""
@@ -50,6 +56,8 @@ def main(argv=None):
     print(f"{args.n} rows -> {out} ({time.time() - t0:.3f} s, {gen.engine.ops.name} on {dev}{cond})", flush=True)
     if scores is not None:
         print(f"Avg_JSD {scores[0]!r} Avg_WD {scores[1]!r} (against {args.score_against})", flush=True)
+    if privacy is not None:
+        print(json.dumps(privacy), flush=True)
     return out
 
 

@@ -1,0 +1,1 @@
+from .privacy import DevicePrivacy, PrivacyScores  # noqa: F401

@@ -72,7 +72,38 @@ def _csv_string(s: str) -> str:
     return " " if s == EMPTY else s
 
 
-class DeviceSimilarity:
+class GraphedPass:
+    """A fixed launch sequence ``_launch(values, n)`` over buffers allocated at construction, replayed as a hipGraph.
+    The evaluator provides ``device``, ``max_rows``, ``n_cols`` and sets ``_graphs = {}``, ``_staged = None``."""
+
+    def _replay(self, values: torch.Tensor, n: int) -> None:
+        # a captured pass reads the buffer it was captured on: generate_decoded returns the same one per n, so the
+        # first few (n, buffer) pairs get a graph of their own; any further table is staged into one of ours
+        g = self._graphs.get((n, values.data_ptr()))
+        if g is None and len(self._graphs) >= MAX_GRAPHS:
+            if self._staged is None:
+                self._staged = torch.empty(self.max_rows, self.n_cols, dtype=torch.float64, device=self.device)
+            stage = self._staged[:n]
+            stage.copy_(values)
+            values = stage
+            g = self._graphs.get((n, values.data_ptr()))
+        key = (n, values.data_ptr())
+        if g is None:
+            cur = torch.cuda.current_stream(self.device)
+            s = torch.cuda.Stream(self.device)
+            s.wait_stream(cur)
+            with torch.cuda.stream(s):       # warm-up outside the capture
+                self._launch(values, n)
+            cur.wait_stream(s)
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._launch(values, n)
+            self._graphs[key] = g
+        g.replay()
+
+
+class DeviceSimilarity(GraphedPass):
     def __init__(self, real: pd.DataFrame, meta: dict, vocabs: Sequence, device, ops=None, max_rows: int = 40000,
                  graph: bool = False):
         if meta.get("date_info"):
@@ -164,32 +195,6 @@ class DeviceSimilarity:
         ops.sim_w1(self.real_keys, self.n_real, self.keys, self.valid, n, self._wd, self.part)
         ops.sim_jsd(self.real_counts, self.counts, self._jsd)
         ops.sim_mean(self.scores, self.n_cat, self.n_cont)
-
-    def _replay(self, values: torch.Tensor, n: int) -> None:
-        # a captured pass reads the buffer it was captured on: generate_decoded returns the same one per n, so the
-        # first few (n, buffer) pairs get a graph of their own; any further table is staged into one of ours
-        g = self._graphs.get((n, values.data_ptr()))
-        if g is None and len(self._graphs) >= MAX_GRAPHS:
-            if self._staged is None:
-                self._staged = torch.empty(self.max_rows, self.n_cols, dtype=torch.float64, device=self.device)
-            stage = self._staged[:n]
-            stage.copy_(values)
-            values = stage
-            g = self._graphs.get((n, values.data_ptr()))
-        key = (n, values.data_ptr())
-        if g is None:
-            cur = torch.cuda.current_stream(self.device)
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(cur)
-            with torch.cuda.stream(s):       # warm-up outside the capture
-                self._launch(values, n)
-            cur.wait_stream(s)
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._launch(values, n)
-            self._graphs[key] = g
-        g.replay()
 
     def score(self, values: torch.Tensor) -> SimilarityScores:
         """values: [n, n_cols] float64 on the evaluator's device, as ``generate_decoded`` returns them.  The work is

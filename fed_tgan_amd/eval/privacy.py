@@ -1,0 +1,206 @@
+"""On-device privacy evaluator: DCR / NNDR of a decoded table against the real one.
+
+Did the generator memorise real records?  The usual answer (CTAB-GAN and its successors report it) is two
+nearest-neighbour metrics of every synthetic row against the real table:
+
+* DCR, the distance to the closest record;
+* NNDR, the nearest-neighbour distance ratio: nearest distance over second-nearest distance;
+
+each reported as the 5th percentile over the synthetic rows, next to the same two numbers inside the real table
+(every real row against the others), which serve as the baseline.
+
+Rows live in the space of the decoded table (``generate_decoded``'s ``[n, n_cols]`` float64: label codes in the
+categorical columns, log1p values in the ``non_negative_cols``, no integer rounding).  The real table is brought
+there once: :class:`fed_tgan_amd.data.table.TablePreprocessor` with the lists ``meta`` carries, then the
+vocabularies' codes, a real category outside a vocabulary getting a code past its end (it never equals a generated
+code).  Continuous column c maps to ``(v - lo_c) * s_c`` with ``lo_c``, ``hi_c`` the real table's extremes and
+``s_c = 1 / (hi_c - lo_c)`` (1 for a constant column), and
+
+    d2(q, r) = sum over continuous columns of (q_c - r_c)^2 + number of categorical columns whose codes differ
+
+in float64 from direct differences, so a copied record is at distance exactly 0.  DCR = sqrt(d1), NNDR =
+sqrt(d1 / d2) with d1 <= d2 the two smallest d2 (with multiplicity), NNDR = 1 where d2 == 0 and 0 where there is no
+second candidate.
+
+``score(values)`` is a fixed launch sequence (``ops.nn_pack`` -> ``nn_top2`` -> ``nn_stats``) over buffers allocated
+at construction, without allocation or host round trip, so it can be captured in a hipGraph (``graph=True``).  The
+ops come from :class:`fed_tgan_amd.ops.hip.HipOps` (kernels/privacy.hip) on a GPU and from
+:class:`fed_tgan_amd.ops.ref.TorchOps` elsewhere; the second is the first's oracle.
+"""
+from __future__ import annotations
+
+from typing import Dict, Sequence, Tuple
+
+import numpy as np
+import pandas as pd
+import torch
+
+from ..data.constants import CATEGORICAL
+from ..data.decode import meta_column_names
+from ..data.table import TablePreprocessor
+from .device import GraphedPass
+
+NN_CONT, NN_CAT = 0, 1
+KEYS = ("dcr_p5", "nndr_p5", "dcr_min", "copies", "dcr_rr_p5", "nndr_rr_p5")
+
+
+class PrivacyScores:
+    """Scores of one table: ``buf`` = [dcr_p5, nndr_p5, dcr_min, copies, dcr_rr_p5, nndr_rr_p5] on the device.
+    Nothing here synchronises except :meth:`floats`."""
+
+    def __init__(self, buf: torch.Tensor, d1: torch.Tensor, d2: torch.Tensor, i1: torch.Tensor):
+        self.buf = buf
+        self._d1, self._d2, self._i1 = d1, d2, i1
+
+    def floats(self) -> Dict[str, float]:
+        return {k: float(v) for k, v in zip(KEYS, self.buf.cpu().tolist())}
+
+    def rows(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """per-row (DCR, NNDR, index of a nearest real row) as device tensors"""
+        d1, d2 = self._d1, self._d2
+        none = torch.isinf(d2)
+        ratio = torch.sqrt(torch.where(none, torch.zeros_like(d1), d1) /
+                           torch.where(none | (d2 == 0), torch.ones_like(d2), d2))
+        return torch.sqrt(d1), torch.where(d2 == 0, torch.ones_like(ratio), ratio), self._i1
+
+
+def code_real_table(real: pd.DataFrame, meta: dict, vocabs: Sequence) -> np.ndarray:
+    """The real frame in the row space of the decoded table: float64 [m, n_cols], columns in ``meta``'s order."""
+    names = meta_column_names(meta)
+    missing = [n for n in names if n not in real.columns]
+    if missing:
+        raise ValueError(f"DevicePrivacy: the real table lacks columns {missing[:5]}")
+    cats = [c["column_name"] for c in meta["columns"] if c["type"] == CATEGORICAL]
+    tp = TablePreprocessor(real[names], "real", str(meta.get("problem_type") or ""), str(meta.get("target") or ""),
+                           cats, list(meta.get("non_negative_cols") or []))
+    out = np.empty((len(tp.df), len(names)), dtype=np.float64)
+    cursor = 0
+    for j, name in enumerate(names):
+        if name in cats:
+            codes, labels = tp._cat_strings(name)
+            vocab = vocabs[cursor]
+            cursor += 1
+            idx = pd.Index(vocab.classes_).get_indexer(np.asarray([str(s) for s in labels], dtype=object))
+            unseen = idx < 0         # codes past the vocabulary: never equal to a generated code
+            idx[unseen] = len(vocab) + np.arange(int(unseen.sum()))
+            out[:, j] = idx[codes]
+        else:
+            v = pd.to_numeric(tp.df[name], errors="coerce").to_numpy(dtype=np.float64)
+            if not np.isfinite(v).all():
+                raise ValueError(f"DevicePrivacy: the real column {name!r} holds a value that is not a finite number")
+            out[:, j] = v
+    return out
+
+
+class DevicePrivacy(GraphedPass):
+    def __init__(self, real, meta: dict, vocabs: Sequence, device, ops=None, max_rows: int = 40000,
+                 baseline: bool = True, graph: bool = False):
+        """real: the real table as a DataFrame, or already coded as a float64 [m, n_cols] array."""
+        if meta.get("date_info"):
+            raise ValueError("DevicePrivacy: the table has date columns; the decoded table holds their parts, not "
+                             "the dates, so rows would not be comparable")
+        self.device = torch.device(device)
+        if ops is None:
+            if self.device.type == "cuda":
+                from ..ops.hip import HipOps
+                ops = HipOps(self.device)
+            else:
+                from ..ops.ref import TorchOps
+                ops = TorchOps()
+        self.ops = ops
+        self.max_rows = int(max_rows)
+        if self.max_rows < 1:
+            raise ValueError("DevicePrivacy: max_rows must be >= 1")
+        names = meta_column_names(meta)
+        self.n_cols = len(names)
+        kind = [NN_CAT if c["type"] == CATEGORICAL else NN_CONT for c in meta["columns"]]
+        slot, n_cat, n_cont = [], 0, 0
+        for k in kind:
+            slot.append(n_cat if k == NN_CAT else n_cont)
+            n_cat += k == NN_CAT
+            n_cont += k == NN_CONT
+        self.n_cat, self.n_cont = n_cat, n_cont
+        if isinstance(real, pd.DataFrame):
+            coded = code_real_table(real, meta, vocabs)
+        else:
+            coded = np.ascontiguousarray(np.asarray(real, dtype=np.float64))
+            if coded.ndim != 2 or coded.shape[1] != self.n_cols:
+                raise ValueError(f"DevicePrivacy: expected a coded [m, {self.n_cols}] real table, got {coded.shape}")
+            for j, k in enumerate(kind):
+                if k == NN_CONT and not np.isfinite(coded[:, j]).all():
+                    raise ValueError(f"DevicePrivacy: the real column {names[j]!r} holds a value that is not a "
+                                     "finite number")
+        m = coded.shape[0]
+        if m < 1:
+            raise ValueError("DevicePrivacy: the real table is empty")
+        self.n_real = m
+        dev = self.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.kind = torch.tensor(kind, **i32)
+        self.slot = torch.tensor(slot, **i32)
+        table = torch.from_numpy(np.ascontiguousarray(coded)).to(dev)
+        cont_cols = torch.tensor([j for j, k in enumerate(kind) if k == NN_CONT], dtype=torch.long, device=dev)
+        # MinMax on real, as stat_sim scales: lo and 1 / (hi - lo) of the real columns (1 for a constant column)
+        rc = table[:, cont_cols]
+        self.lo = rc.min(dim=0).values.contiguous() if n_cont else torch.zeros(0, **f64)
+        hi = rc.max(dim=0).values if n_cont else torch.zeros(0, **f64)
+        span = hi - self.lo
+        self.scale = torch.where(span > 0, 1.0 / torch.where(span > 0, span, torch.ones_like(span)),
+                                 torch.ones_like(span)).contiguous()
+        self.r_cont = torch.zeros(m, n_cont, **f64)
+        self.r_cat = torch.zeros(m, n_cat, **i32)
+        ops.nn_pack(table, self.kind, self.slot, self.lo, self.scale, self.r_cont, self.r_cat)
+        self.scores = torch.zeros(len(KEYS), **f64)
+        self.scores[4:] = float("nan")
+        if baseline:        # every real row against the others, once, over buffers of its own
+            self._alloc(m)
+            self._stats(self.r_cont, self.r_cat, m, True)
+            self.scores[4:6] = self.scores[0:2]
+            self.scores[:4] = 0.0
+        self._alloc(self.max_rows)
+        self.graph = bool(graph) and dev.type == "cuda"
+        self._graphs: Dict[Tuple[int, int], object] = {}
+        self._staged = None
+
+    def _alloc(self, rows: int) -> None:
+        ops, dev = self.ops, self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.q_cont = torch.zeros(rows, self.n_cont, **f64)
+        self.q_cat = torch.zeros(rows, self.n_cat, dtype=torch.int32, device=dev)
+        self.d1 = torch.zeros(rows, **f64)
+        self.d2 = torch.zeros(rows, **f64)
+        self.i1 = torch.zeros(rows, dtype=torch.int32, device=dev)
+        self.scratch = torch.zeros(ops.nn_scratch(rows, self.n_real), **f64)
+        self.keys = torch.zeros(2, rows, **f64)
+        self.tmp = torch.zeros(2, rows, **f64)
+        self.part = torch.zeros(ops.nn_stats_part(rows), **f64)
+
+    # ------------------------------------------------------------------ the pass
+    def _stats(self, q_cont: torch.Tensor, q_cat: torch.Tensor, n: int, exclude_self: bool) -> None:
+        ops = self.ops
+        ops.nn_top2(q_cont, q_cat, self.r_cont, self.r_cat, exclude_self, self.d1, self.d2, self.i1, self.scratch)
+        ops.nn_stats(self.d1, self.d2, n, self.keys, self.tmp, self.part, self.scores)
+
+    def _launch(self, values: torch.Tensor, n: int) -> None:
+        self.ops.nn_pack(values, self.kind, self.slot, self.lo, self.scale, self.q_cont, self.q_cat)
+        self._stats(self.q_cont[:n], self.q_cat[:n], n, False)
+
+    def score(self, values: torch.Tensor) -> PrivacyScores:
+        """values: [n, n_cols] float64 on the evaluator's device, as ``generate_decoded`` returns them (finite
+        values are a precondition).  The work is queued on the current stream; the returned scores are device
+        tensors and nothing waits for them."""
+        if values.dim() != 2 or values.shape[1] != self.n_cols or values.dtype != torch.float64:
+            raise ValueError(f"score: expected a float64 [n, {self.n_cols}] table, got {tuple(values.shape)} "
+                             f"{values.dtype}")
+        if values.device != self.keys.device:
+            raise ValueError(f"score: the table is on {values.device}, the evaluator on {self.keys.device}")
+        n = int(values.shape[0])
+        if n < 1 or n > self.max_rows:
+            raise ValueError(f"score: {n} rows; this evaluator's buffers hold 1..{self.max_rows}")
+        values = values.contiguous()
+        if self.graph:
+            self._replay(values, n)
+        else:
+            self._launch(values, n)
+        return PrivacyScores(self.scores.clone(), self.d1[:n].clone(), self.d2[:n].clone(), self.i1[:n].clone())

@@ -59,6 +59,7 @@ class LoadedGenerator:
     meta: dict
     vocabs: list
     _similarity: dict = dataclasses.field(default_factory=dict, repr=False)   # (real table, n) -> its evaluator
+    _privacy: dict = dataclasses.field(default_factory=dict, repr=False)      # the same for privacy()
 
     def sample(self, n: int, where=None, max_passes: int = 64) -> np.ndarray:
         """[n, n_columns] decoded values (label codes for categoricals), float64.  A GPU table comes
@@ -102,10 +103,36 @@ class LoadedGenerator:
     def write_csv_scored(self, path: str, n: int, real, threads: int = 0, where=None, max_passes: int = 64):
         """:meth:`write_csv` and :meth:`score` of the same n rows: the table is scored on the device while it is
         still there, then copied and written.  Returns (Avg_JSD, Avg_WD)."""
+        return self.write_csv_evaluated(path, n, score_real=real, threads=threads, where=where,
+                                        max_passes=max_passes)[0]
+
+    def write_csv_evaluated(self, path: str, n: int, score_real=None, privacy_real=None, threads: int = 0, where=None,
+                            max_passes: int = 64):
+        """:meth:`write_csv` with :meth:`score` (score_real) and / or :meth:`privacy` (privacy_real) of the rows the
+        CSV holds, both taken on the device before the copy.  Returns ((Avg_JSD, Avg_WD) | None, privacy dict | None)."""
         vals = self.device_table(n, where=where, max_passes=max_passes)
-        scores = self._evaluator(real, n).score(vals)
+        sim = self._evaluator(score_real, n).score(vals) if score_real is not None else None
+        priv = self._privacy_evaluator(privacy_real, n).score(vals) if privacy_real is not None else None
         self._write_values(path, self._to_host(vals), threads)
-        return scores.floats()
+        return (sim.floats() if sim is not None else None), (priv.floats() if priv is not None else None)
+
+    def privacy(self, real, n: int = 40000, where=None, max_passes: int = 64) -> dict:
+        """DCR / NNDR of n generated rows against ``real`` (a DataFrame or a CSV path): generated and scored on the
+        engine's device (eval/privacy.py), only the six numbers come back: the 5th percentiles ``dcr_p5`` /
+        ``nndr_p5``, ``dcr_min``, the share of exact ``copies``, and the real table's own ``dcr_rr_p5`` /
+        ``nndr_rr_p5`` as the baseline.  The evaluator is kept per real table and n."""
+        return self._privacy_evaluator(real, n).score(self.device_table(n, where=where, max_passes=max_passes)).floats()
+
+    def _privacy_evaluator(self, real, n: int):
+        import pandas as pd
+        from ..eval.privacy import DevicePrivacy
+        key = (real if isinstance(real, str) else id(real), int(n))
+        if key not in self._privacy:
+            frame = pd.read_csv(real) if isinstance(real, str) else real
+            self._privacy.clear()
+            self._privacy[key] = (frame, DevicePrivacy(frame, self.meta, self.vocabs, self.engine.device,
+                                                       ops=self.engine.ops, max_rows=int(n)))
+        return self._privacy[key][1]
 
     def _evaluator(self, real, n: int):
         import pandas as pd

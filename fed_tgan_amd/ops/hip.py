@@ -622,3 +622,39 @@ class HipOps:
 
     def sim_mean(self, scores, n_cat, n_cont):
         self.L.sim_mean(scores, int(n_cat), int(n_cont))
+
+    # ------------------------------------------------------------------ privacy evaluator (kernels/privacy.hip)
+    NN_CONT, NN_CAT = 0, 1
+    NN_QUERY_TILE = 256     # kernels/launch.h: query rows per workgroup
+    NN_REF_TILE = 16        # reference rows staged in LDS at a time
+    NN_CHUNK_ROWS = 2048    # reference rows per chunk of the grid
+
+    @staticmethod
+    def nn_chunks(nr: int) -> int:
+        """reference chunks (partials per query) nn_top2 uses for nr reference rows"""
+        return int(native.require().nn_chunks(int(nr)))
+
+    @staticmethod
+    def nn_scratch(nq: int, nr: int) -> int:
+        """float64 scratch elements nn_top2 needs for nq queries against nr reference rows"""
+        return int(native.require().nn_scratch(int(nq), int(nr)))
+
+    @staticmethod
+    def nn_stats_part(n: int) -> int:
+        """float64 scratch elements nn_stats needs for n rows"""
+        return int(native.require().nn_stats_part(int(n)))
+
+    def nn_pack(self, values, kind, slot, lo, scale, cont, cat):
+        """Same contract as TorchOps.nn_pack."""
+        self.L.nn_pack(values, kind, slot, lo, scale, cont, cat)
+
+    def nn_top2(self, q_cont, q_cat, r_cont, r_cat, exclude_self, d1, d2, i1, scratch):
+        """Same contract as TorchOps.nn_top2; scratch: float64 [>= nn_scratch(nq, nr)]."""
+        self.L.nn_top2(q_cont, q_cat, r_cont, r_cat, bool(exclude_self), d1, d2, i1, scratch)
+
+    def nn_stats(self, d1, d2, n, keys, tmp, part, out):
+        """Same contract as TorchOps.nn_stats; tmp: scratch of keys' shape (the sort's), part: float64
+        [>= nn_stats_part(n)]."""
+        self.L.nn_stats(d1, d2, int(n), keys, part)
+        self.L.sim_sort(keys, tmp, int(n))
+        self.L.nn_percentiles(keys, int(n), part, out)

@@ -494,3 +494,97 @@ class TorchOps:
         """scores = [avg_jsd, avg_wd, jsd x n_cat, wd x n_cont]: the first two from the rest (NaN: no such column)."""
         scores[0] = scores[2:2 + n_cat].mean() if n_cat else float("nan")
         scores[1] = scores[2 + n_cat:2 + n_cat + n_cont].mean() if n_cont else float("nan")
+
+    # ------------------------------------------------------------------ privacy evaluator
+    NN_CONT, NN_CAT = 0, 1
+    NN_QUERY_TILE, NN_REF_TILE, NN_CHUNK_ROWS = 256, 16, 2048   # the HIP kernels' tiles; shared attributes only
+    NN_PAIRS = 1 << 24                                           # d2 entries nn_top2 holds at a time
+
+    @staticmethod
+    def nn_chunks(nr: int) -> int:
+        return 1
+
+    @staticmethod
+    def nn_scratch(nq: int, nr: int) -> int:
+        return 1
+
+    @staticmethod
+    def nn_stats_part(n: int) -> int:
+        return 1
+
+    def nn_pack(self, values, kind, slot, lo, scale, cont, cat):
+        """One pass over a decoded table values [n, n_cols] float64 (eval/privacy.py DevicePrivacy).
+
+        kind / slot int32 [n_cols]: a continuous column (NN_CONT) becomes column slot of cont [>= n, n_cont] as
+        (v - lo[slot]) * scale[slot], one subtraction and one product in float64; a categorical column (NN_CAT)
+        becomes column slot of cat [>= n, n_cat] int32, its code truncated to an integer (a value outside
+        [0, 2^31 - 1), or NaN: -1, which equals no code)."""
+        n = values.shape[0]
+        for c, (k, s) in enumerate(zip(kind.tolist(), slot.tolist())):
+            v = values[:, c]
+            if k == self.NN_CAT:
+                ok = (v >= 0) & (v < 2147483647.0)
+                cat[:n, s] = torch.where(ok, v, torch.full_like(v, -1.0)).to(cat.dtype)
+            else:
+                cont[:n, s] = (v - lo[s]) * scale[s]
+
+    def nn_top2(self, q_cont, q_cat, r_cont, r_cat, exclude_self, d1, d2, i1, scratch=None):
+        """Per query row i the two smallest squared distances d1[i] <= d2[i] to the reference rows, counted with
+        multiplicity, and i1[i] (int32) the lowest index of a reference row at distance d1[i].
+
+        d2(q, r) = sum over the continuous columns, in column order, of (q_c - r_c)^2 plus the number of
+        categorical columns whose codes differ, in float64 from direct differences.  exclude_self: reference row
+        i is no candidate of query i (a table against itself).  Fewer than two candidates: d2 = +inf; none:
+        d1 = +inf, i1 = -1.  Works on blocks of queries, so the full distance matrix never exists."""
+        nq, nr = q_cont.shape[0], r_cont.shape[0]
+        dev = q_cont.device
+        inf = float("inf")
+        step = max(1, self.NN_PAIRS // max(nr, 1))
+        cols = torch.arange(nr, device=dev)
+        for q0 in range(0, nq, step):
+            q1 = min(nq, q0 + step)
+            dist = torch.zeros(q1 - q0, nr, dtype=torch.float64, device=dev)
+            for c in range(q_cont.shape[1]):
+                diff = q_cont[q0:q1, c, None] - r_cont[None, :, c]
+                dist += diff * diff
+            if q_cat.shape[1]:
+                miss = torch.zeros(q1 - q0, nr, dtype=torch.int32, device=dev)
+                for c in range(q_cat.shape[1]):
+                    miss += (q_cat[q0:q1, c, None] != r_cat[None, :, c]).to(torch.int32)
+                dist += miss.to(torch.float64)
+            rows = torch.arange(q1 - q0, device=dev)
+            if exclude_self:
+                own = rows + q0
+                ok = own < nr
+                dist[rows[ok], own[ok]] = inf
+            best = dist.min(dim=1).values
+            first = torch.where(dist == best[:, None], cols[None, :], nr).min(dim=1).values     # lowest index of a tie
+            none = torch.isinf(best)
+            first = torch.where(none, torch.zeros_like(first), first)
+            dist[rows, first] = inf
+            d1[q0:q1] = best
+            d2[q0:q1] = dist.min(dim=1).values
+            i1[q0:q1] = torch.where(none, torch.full_like(first, -1), first).to(i1.dtype)
+
+    def nn_stats(self, d1, d2, n, keys, tmp, part, out):
+        """Table scores of rows [0, n): keys [2, >= n] receives DCR = sqrt(d1) and NNDR = sqrt(d1 / d2) (1 where
+        d2 == 0, 0 where d2 = +inf), each row ascending; out[0], out[1] = their 5th percentiles with numpy's linear
+        interpolation at position 0.05 (n - 1); out[2] = the smallest DCR; out[3] = the share of rows with d1 == 0."""
+        a, b = d1[:n], d2[:n]
+        safe = torch.where((b == 0) | torch.isinf(b), torch.ones_like(b), b)
+        ratio = torch.sqrt(torch.where(torch.isinf(b), torch.zeros_like(a), a) / safe)
+        ratio = torch.where(b == 0, torch.ones_like(ratio), ratio)
+        keys[0, :n] = torch.sort(torch.sqrt(a)).values
+        keys[1, :n] = torch.sort(ratio).values
+        pos = (n - 1) * 0.05
+        lo = min(max(int(math.floor(pos)), 0), n - 1)
+        hi = min(lo + 1, n - 1)
+        t = pos - lo
+        for row in range(2):
+            u, v = keys[row, lo], keys[row, hi]
+            if t == 0.0 or bool(u == v):
+                out[row] = u
+            else:       # numpy's _lerp
+                out[row] = v - (v - u) * (1.0 - t) if t >= 0.5 else u + (v - u) * t
+        out[2] = keys[0, 0]
+        out[3] = (a == 0).sum().to(torch.float64) / n
