@@ -29,6 +29,7 @@ import torch
 
 from ..data.constants import CATEGORICAL, EMPTY
 from ..data.decode import meta_column_names
+from ..utils.devsync import warm_and_capture
 
 SIM_PLAIN, SIM_NONNEG, SIM_CAT = 0, 1, 2
 MAX_GRAPHS = 4     # captured passes that read the caller's own buffer; tables beyond them are staged into ours
@@ -89,16 +90,9 @@ class GraphedPass:
             g = self._graphs.get((n, values.data_ptr()))
         key = (n, values.data_ptr())
         if g is None:
-            cur = torch.cuda.current_stream(self.device)
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(cur)
-            with torch.cuda.stream(s):       # warm-up outside the capture
+            def launch():
                 self._launch(values, n)
-            cur.wait_stream(s)
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._launch(values, n)
+            g, = warm_and_capture(self.device, launch, [launch])
             self._graphs[key] = g
         g.replay()
 

@@ -47,6 +47,18 @@ class TorchAlloc:
         return t.to(self.device, copy=True).contiguous() if t.device != self.device else t.clone().contiguous()
 
 
+def _ceil4(n: int) -> int:
+    return (int(n) + 3) // 4 * 4
+
+
+def _padded_rows(rows: int, cols: int, mem) -> torch.Tensor:
+    """[rows, cols] view of a zeroed [rows, ceil4(cols)] buffer (16-B aligned row starts); ``mem`` is an
+    allocator or a device."""
+    if not hasattr(mem, "zeros"):
+        mem = TorchAlloc(mem)
+    return mem.zeros(rows, _ceil4(cols), dtype=torch.float32)[:, :cols]
+
+
 class _Slab(TorchAlloc):
     def __init__(self, arena: "Arena", c: int):
         super().__init__(arena.device)

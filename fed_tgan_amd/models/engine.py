@@ -44,23 +44,13 @@ import numpy as np
 import torch
 
 from ..features.transformer import SpanLayout
-from .arena import TorchAlloc
+from ..utils.devsync import warm_and_capture
+from .arena import TorchAlloc, _ceil4, _padded_rows
 from .ctgan import Discriminator, Generator
+from .generation import GenerationMixin
 from .samplers import CondTables, RowIndex
 
 EPI_NONE, EPI_LRELU_DROPOUT, EPI_MASK, EPI_RELU = 0, 1, 2, 3
-
-
-def _ceil4(n: int) -> int:
-    return (int(n) + 3) // 4 * 4
-
-
-def _padded_rows(rows: int, cols: int, mem) -> torch.Tensor:
-    """[rows, cols] view of a zeroed [rows, ceil4(cols)] buffer (16-B aligned row starts); ``mem`` is an
-    allocator (models/arena.py) or a device."""
-    if not hasattr(mem, "zeros"):
-        mem = TorchAlloc(mem)
-    return mem.zeros(rows, _ceil4(cols), dtype=torch.float32)[:, :cols]
 
 
 def _ext(t: torch.Tensor, cols: int) -> torch.Tensor:
@@ -191,7 +181,7 @@ def get_ops(backend: str, device: torch.device, seed: int = 0, precision: str = 
     raise ValueError(backend)
 
 
-class CTGANEngine:
+class CTGANEngine(GenerationMixin):
     def __init__(self, layout: SpanLayout, cfg: EngineConfig | None = None, device="cpu", backend: str = "auto",
                  seed: int | None = None, mem=None):
         self.cfg = cfg = cfg or EngineConfig()
@@ -237,14 +227,9 @@ class CTGANEngine:
         if self.device.type == "cuda" and cfg.streams:
             self.lanes = [None] + [torch.cuda.Stream(self.device) for _ in range(3)]
         self.tables: Dict[str, torch.Tensor] = {}
-        self.gen_tables = None
-        self._gen_bufs = None
-        self._gen_graphs: Dict[int, tuple] = {}   # n -> (hipGraph, H, logits, out) of generate_decoded
-        self._gen_split: Dict[int, tuple] = {}    # n -> (prep graph, body graph, H, logits, out, col, opt)
-        self._gen_done = None                     # event: the last pipelined generation body has finished
-        self._cond_ent: Dict[tuple, dict] = {}    # (m, bins, fixed columns) -> buffers / hipGraph of a conditional pass
-        self.last_conditional = None              # generate_decoded_where: passes, rows generated / kept, filled counts
+        self._init_generation()   # table generation: models/generation.py
         self.graphs: Dict[int, object] = {}    # steps per graph -> captured hipGraph
+        self.lead_event = self._lead_ev = None    # train_steps(lead=...): the event before the last blocks
         self.capture_mode = "global"   # "thread_local" when several engines capture from threads
         self.bn_batches = 0       # num_batches_tracked of every BN layer
         self.batch = None         # models/batched.py BatchedClients when this engine issues K clients' steps
@@ -620,36 +605,6 @@ class CTGANEngine:
         self.tables = t
         self.steps_per_epoch = len(encoded) // self.B
         self.graphs = {}
-
-    def set_generation_tables(self, cond: CondTables, transformer):
-        """Tables for sample_zero + fused decode (transformer: a fitted VGMTransformer)."""
-        dev = self.device
-        self.gen_cond = {
-            "cdf_emp": torch.as_tensor(cond.cdf_emp, dtype=torch.float32, device=dev),
-            "cond_offset": torch.as_tensor(self.layout.cond_offset, dtype=torch.int32, device=dev),
-            "cond_width": torch.as_tensor(self.layout.cond_width, dtype=torch.int32, device=dev),
-        }
-        mu, sd = transformer.decode_tables()
-        cols = []
-        pos = 0
-        c = 0
-        for j, m in enumerate(transformer.meta):
-            if m["type"] == "continuous":
-                nv = int(transformer.components[c].sum())
-                cols.append((0, pos, nv, c, None))
-                pos += 1 + nv
-                c += 1
-            else:
-                w = int(m["size"])
-                codes = torch.as_tensor(np.asarray(m["i2s"], dtype=np.float64), device=dev)
-                cols.append((1, pos, w, -1, codes))
-                pos += w
-        self.gen_tables = {"cols": cols, "mu": torch.as_tensor(mu, dtype=torch.float64, device=dev),
-                           "sd": torch.as_tensor(sd, dtype=torch.float64, device=dev)}
-        self._gen_bufs = None
-        self._gen_graphs = {}
-        self._gen_split = {}
-        self._cond_ent = {}
 
     # ================================================================= forward pieces
     def _kpad(self, H, a: int, W: torch.Tensor):
@@ -1140,7 +1095,7 @@ class CTGANEngine:
         self.train_steps(self.steps_per_epoch, use_graph, lead)
 
     def _mark_lead(self):
-        if getattr(self, "_lead_ev", None) is None:
+        if self._lead_ev is None:
             self._lead_ev = torch.cuda.Event()
         self._lead_ev.record(torch.cuda.current_stream(self.device))
         self.lead_event = self._lead_ev
@@ -1166,7 +1121,7 @@ class CTGANEngine:
         ``generate_decoded(n)`` for ``n`` in ``gen_rows`` will replay: the capture (one eager warm-up step
         or pass plus the capture itself, ~40 ms for the Intrusion step graph) then happens at
         initialisation instead of inside round 0's timed window.  Capturing never changes the training
-        state (``_capture_locked`` restores it).  No-op off the GPU / without graphs."""
+        state (``_capture`` restores it).  No-op off the GPU / without graphs."""
         if self.device.type != "cuda":
             return
         steps = self.steps_per_epoch if steps is None else int(steps)
@@ -1182,13 +1137,7 @@ class CTGANEngine:
                 self._capture(U)
             if rest % U and self._graph_key(1) not in self.graphs:
                 self._capture(1)
-        if self.gen_tables is not None and self.cfg.gen_graph and self.ops.name == "hip":
-            for n in gen_rows:
-                if n > 0 and gen_split and self.can_split_generation():
-                    if n not in self._gen_split:
-                        self._capture_gen_split(int(n))
-                elif n > 0 and n not in self._gen_graphs:
-                    self._capture_gen(int(n))
+        self._prepare_generation_graphs(gen_rows, gen_split)
 
     def _graph_key(self, steps: int):
         """Captured step graphs are per (steps, clients): a batched engine whose clients hold different row
@@ -1197,50 +1146,38 @@ class CTGANEngine:
         return steps if k == 1 else (steps, k)
 
     def _capture(self, steps: int = 1):
-        from ..utils.devsync import CAPTURE_LOCK
-        with CAPTURE_LOCK:      # no device-wide sync from another client thread meanwhile
-            return self._capture_locked(steps)
-
-    def _capture_locked(self, steps: int = 1):
-        # warm up on a side stream (allocator / lazy init), then capture one step.  The state snapshot is
-        # enqueued BEFORE the side stream forks from the current one, so the warm-up step cannot overtake
-        # the copies (it could, racing them, when the fork came first).  (A batched engine's warm-up step
-        # trains every client: all of their states are restored.)
+        # one eager warm-up step (allocator / lazy init), then the capture (utils/devsync.py warm_and_capture).  The
+        # warm-up step does not count: the training state is snapshot before it and restored after it -- also when
+        # it raised part-way (e.g. a batched arena slab overflow): the caller may fall back to other engines that
+        # copy this state.  (A batched engine's warm-up step trains every client: all of their states are restored.)
         # (the device Philox counter too: a capture must not shift the clients' random streams, whatever step of
         # an epoch -- or which epoch segment of a batched engine with ragged clients -- it happens at)
         state = self.batch.state_tensors() if self.batch is not None else \
             [self.flat, self.mG, self.vG, self.mD, self.vD] + \
             ([self._step_sets] if self._multi else [self.stepG, self.stepD]) + \
             ([self.ops.ctr] if hasattr(self.ops, "ctr") else [])
-        snap = [t.clone() for t in state]
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        try:
-            with torch.cuda.stream(s):
-                self._one_step()
-        finally:
-            # restore the state so the warm-up step does not count -- also when it raised part-way (e.g. a
-            # batched arena slab overflow): the caller may fall back to other engines that copy this state
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            torch.cuda.synchronize(self.device)
+        multi = self._multi and steps % self._U == 0 and self.batch is None
+
+        def restore(snap):
             for dst, src in zip(state, snap):
                 dst.copy_(src)
-        g = torch.cuda.CUDAGraph()
-        multi = self._multi and steps % self._U == 0 and self.batch is None
+
+        def body():
+            if multi:
+                # one launch draws every step's batch of a block into its own buffer set; step k then runs on
+                # set k with its own optimizer counters / metrics (written by that launch); blocks repeat
+                for _ in range(steps // self._U):
+                    self._bind_set(0, 0)
+                    self._draw_all()
+                    for k in range(self._U):
+                        self._bind_set(k, k)
+                        self._one_step(draw=False)
+            else:
+                for _ in range(steps):      # every step re-reads the device RNG/step counters
+                    self._one_step()
         try:
-            with torch.cuda.graph(g, capture_error_mode=self.capture_mode):
-                if multi:
-                    # one launch draws every step's batch of a block into its own buffer set; step k then runs on
-                    # set k with its own optimizer counters / metrics (written by that launch); blocks repeat
-                    for _ in range(steps // self._U):
-                        self._bind_set(0, 0)
-                        self._draw_all()
-                        for k in range(self._U):
-                            self._bind_set(k, k)
-                            self._one_step(draw=False)
-                else:
-                    for _ in range(steps):      # every step re-reads the device RNG/step counters
-                        self._one_step()
+            g, = warm_and_capture(self.device, self._one_step, [body], snapshot=lambda: [t.clone() for t in state],
+                                  restore=restore, mode=self.capture_mode)
         finally:
             if multi:
                 self._bind_set(0)
@@ -1255,9 +1192,7 @@ class CTGANEngine:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         self.graphs.clear()
-        self._gen_graphs.clear()
-        self._gen_split.clear()
-        self._cond_ent.clear()
+        self._drop_generation()
         self._gen_done = None
 
     @property
@@ -1268,376 +1203,3 @@ class CTGANEngine:
     def losses(self) -> Tuple[float, float]:
         m = self.metrics.detach().cpu().numpy()
         return float(m[0] + m[1]), float(m[2] + m[3])
-
-    # ================================================================= generation
-    @torch.no_grad()
-    def generate_encoded(self, n: int) -> torch.Tensor:
-        """Activated generator output for n rows (eval BN): [n, data_dim]."""
-        out = torch.empty(n, self.Dd, device=self.device)
-        for a in range(0, n, self.cfg.gen_chunk):
-            b = min(n, a + self.cfg.gen_chunk)
-            H, logits, col, opt = self._gen_buffers(b - a, bf16=False)
-            self.ops.sample_gen(self.gen_cond, H, self.c_cols, self.z_cols, col_out=col, opt_out=opt, stream_id=21)
-            self._g_forward(H, logits, training=False, nhat=False, cond=(col, opt, True))
-            self.ops.activate(logits, out[a:b], self.spans, self.cfg.tau, stream_id=22)
-        return out
-
-    @torch.no_grad()
-    def generate_decoded(self, n: int, use_graph: bool | None = None) -> torch.Tensor:
-        """Fused sample -> G(eval) -> Gumbel-argmax/tanh decode: [n, n_cols] float64 on device.
-
-        On a GPU the whole pass for a given n (every chunk's sampler, eval-BN GEMMs and decode
-        launches) is captured once into a hipGraph and replayed each round; the result is a fresh
-        tensor (a device copy of the graph's static output)."""
-        if self.gen_tables is None:
-            raise RuntimeError("set_generation_tables() first")
-        if use_graph is None:
-            use_graph = self.device.type == "cuda" and self.cfg.gen_graph and self.ops.name == "hip"
-        if self._gen_done is not None:    # a pipelined body may still read the shared weight copies
-            torch.cuda.current_stream(self.device).wait_event(self._gen_done)
-        if use_graph:
-            ent = self._gen_graphs.get(n) or self._capture_gen(n)
-            ent[0].replay()
-            out = ent[3].clone()
-        else:
-            out = torch.empty(n, len(self.gen_tables["cols"]), dtype=torch.float64, device=self.device)
-            self._gen_pass(n, out, self._gen_buffers)
-        if hasattr(self.ops, "check"):
-            self.ops.check()
-        return out
-
-    # ------------------------------------------------------------------ conditional generation
-    @torch.no_grad()
-    def generate_decoded_where(self, n: int, request: dict, max_passes: int = 64, chunk: int | None = None,
-                               use_graph: bool | None = None) -> torch.Tensor:
-        """Exactly n decoded rows carrying the requested category values: [n, n_cols] float64 on the device, grouped
-        by the driving column's requested values in request order, in generation order (pass, then row) inside a
-        group.  ``request``: models/conditional.py build_request (its quotas sum to n).
-
-        One pass over m rows (``chunk``, default a size fitted to n, at most cfg.gen_chunk): sample_gen ->
-        cond_request (every row's condition becomes the driving column's value of a bin drawn in proportion to the
-        open quotas) -> eval generator -> sample_decode -> cond_partition (rows that carry every requested value move
-        into their bin's quota segment).  The request lives in device buffers, so on the HIP backend with
-        cfg.gen_graph the pass is captured once per (m, bins, fixed columns) and replayed; use_graph=False issues the
-        same launches eagerly, and both give bit-identical tables from equal engine states.  Passes are issued in
-        bursts that cannot overshoot (ceil(open quota / m) of them), with one readback of the filled counters per
-        burst; max_passes passes without every quota full raise ConditionalSamplingError (no partial table).
-        ``self.last_conditional`` records passes, rows generated, rows kept and the per-value counts."""
-        from .conditional import ConditionalSamplingError
-        if self.gen_tables is None:
-            raise RuntimeError("set_generation_tables() first")
-        n = int(n)
-        quotas = [int(q) for q in request["quotas"]]
-        if n != int(request["n"]) or sum(quotas) != n:
-            raise ValueError(f"the request was built for {request['n']} rows, not {n}")
-        n_cols = len(self.gen_tables["cols"])
-        nb, nf = len(quotas), int(request["fixed_j"].numel())
-        if nb > getattr(self.ops, "COND_MAX_BINS", 64):
-            raise ValueError(f"{nb} requested values; the kernels' bin limit is {self.ops.COND_MAX_BINS}")
-        if n == 0:
-            self.last_conditional = {"passes": 0, "generated": 0, "kept": 0, "filled": [0] * nb,
-                                     "values": list(request["values"])}
-            return torch.empty(0, n_cols, dtype=torch.float64, device=self.device)
-        if use_graph is None:
-            use_graph = self.device.type == "cuda" and self.cfg.gen_graph and self.ops.name == "hip"
-        if chunk is not None:
-            m = int(chunk)
-            if m < 1:
-                raise ValueError("chunk must be positive")
-        else:       # a power of two with a quarter of slack for rejected rows: few distinct sizes to capture
-            m = min(int(self.cfg.gen_chunk), max(1024, 1 << int(np.ceil(np.log2(max(1.25 * n, 1.0))))))
-        if self._gen_done is not None:    # a pipelined body may still read the shared weight copies
-            torch.cuda.current_stream(self.device).wait_event(self._gen_done)
-        ent = self._cond_entry(m, nb, nf, n)
-        for k in ("drive", "bin_opt", "bin_code", "quota", "seg_off", "fixed_j", "fixed_code"):
-            ent["req"][k].copy_(request[k])
-        ent["req"]["filled"].zero_()
-        ent["req"]["stats"].zero_()
-        if use_graph and ent.get("graph") is None:
-            self._capture_cond(ent, m)
-        passes, filled = 0, [0] * nb
-        while True:
-            open_rows = sum(q - f for q, f in zip(quotas, filled))
-            if open_rows <= 0:
-                break
-            if passes >= int(max_passes):
-                self.last_conditional = self._cond_report(ent, request, passes, filled)
-                if hasattr(self.ops, "check"):     # (a request pointing outside its tables fills nothing: say that)
-                    self.ops.check()
-                raise ConditionalSamplingError(
-                    f"{passes} passes of {m} rows filled {sum(filled)} of {n} requested rows "
-                    f"(per value: {dict(zip(map(str, request['values']), filled))})", filled, quotas, request["values"])
-            burst = max(1, min(-(-open_rows // m), int(max_passes) - passes))
-            for _ in range(burst):
-                if use_graph:
-                    ent["graph"].replay()
-                else:
-                    self._cond_pass(ent, m)
-            passes += burst
-            filled = [int(x) for x in ent["req"]["filled"].tolist()]     # the one readback per burst
-        out = ent["dst"][:n].clone()
-        self.last_conditional = self._cond_report(ent, request, passes, filled)
-        if hasattr(self.ops, "check"):
-            self.ops.check()
-        return out
-
-    def _cond_report(self, ent, request, passes, filled):
-        st = ent["req"]["stats"].tolist()
-        return {"passes": int(passes), "generated": int(st[0]), "kept": int(st[1]), "filled": list(filled),
-                "values": list(request["values"])}
-
-    def _cond_entry(self, m: int, nb: int, nf: int, n: int) -> dict:
-        """Static buffers of a conditional pass over m rows for requests of nb bins and nf fixed columns: the pass's
-        activations / logits / conditions / targets / decoded rows, the request buffers the launches read, and the
-        quota segments (grown, and the graph dropped, when a request asks for more rows)."""
-        key = (m, nb, nf)
-        ent = self._cond_ent.get(key)
-        dev = self.device
-        if ent is None:
-            H = self._gen_h16(m) if self.gen16 else _padded_rows(m, self.Hw, dev)
-            i32 = lambda k: torch.zeros(k, dtype=torch.int32, device=dev)      # noqa: E731
-            i64 = lambda k: torch.zeros(k, dtype=torch.int64, device=dev)      # noqa: E731
-            f64 = lambda k: torch.zeros(k, dtype=torch.float64, device=dev)    # noqa: E731
-            ent = {"H": H, "lg": _padded_rows(m, self.Dd, dev), "col": i32(m), "opt": i32(m), "tgt": i32(m),
-                   "out": torch.empty(m, len(self.gen_tables["cols"]), dtype=torch.float64, device=dev),
-                   "req": {"drive": i32(2), "bin_opt": i32(nb), "bin_code": f64(nb), "quota": i64(nb),
-                           "filled": i64(nb), "seg_off": i64(nb), "fixed_j": i32(nf), "fixed_code": f64(nf),
-                           "stats": i64(2)},
-                   "dst": None, "graph": None}
-            self._cond_ent[key] = ent
-        if ent["dst"] is None or ent["dst"].shape[0] < n:
-            if ent["graph"] is not None:
-                torch.cuda.synchronize(dev)
-            ent["graph"] = None
-            ent["dst"] = torch.empty(n, len(self.gen_tables["cols"]), dtype=torch.float64, device=dev)
-        return ent
-
-    def _cond_pass(self, ent: dict, m: int):
-        o, req = self.ops, ent["req"]
-        H, lg, col, opt, tgt = ent["H"], ent["lg"], ent["col"], ent["opt"], ent["tgt"]
-        w16 = self._gen_weights16() if self.gen16 else None
-        o.sample_gen(self.gen_cond, H, self.c_cols, self.z_cols, col_out=col, opt_out=opt, stream_id=21)
-        # (stream 24: the request's own Philox stream; 21-23 are the generation sampler's, activation's and decode's)
-        o.cond_request(req, col, opt, tgt, self.gen_cond, h=None if w16 is not None else H, c_col0=self.c_cols[0],
-                       stream_id=24)
-        if w16 is None:
-            self._g_forward(H, lg, training=False, nhat=False, cond=(col, opt, True))
-        else:
-            self._g_forward16(H, lg, w16, (col, opt))
-        o.sample_decode(lg, ent["out"], self.gen_tables, stream_id=23)
-        o.cond_partition(req, ent["out"], tgt, ent["dst"])
-
-    def _capture_cond(self, ent: dict, m: int):
-        """Capture one conditional pass (as _capture_gen).  The warm-up pass sizes every lazily built table and
-        scratch buffer; the RNG counter and the request's counters are put back after it, so a graph-replayed run
-        starts from the state an eager run starts from."""
-        from ..utils.devsync import CAPTURE_LOCK
-        req = ent["req"]
-        with CAPTURE_LOCK:
-            ctr0 = self.ops.ctr.clone()
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                self._cond_pass(ent, m)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            torch.cuda.synchronize(self.device)
-            self.ops.ctr.copy_(ctr0)
-            req["filled"].zero_()
-            req["stats"].zero_()
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=self.capture_mode):
-                self._cond_pass(ent, m)
-        ent["graph"] = g
-
-    # ------------------------------------------------------------------ pipelined generation
-    def can_split_generation(self) -> bool:
-        """generate_decoded_split applies: HIP bf16 generation with graphs."""
-        return (self.device.type == "cuda" and self.gen16 and self.cfg.gen_graph and self.ops.name == "hip" and
-                self.gen_tables is not None and getattr(self.ops, "batch_k", 1) == 1)
-
-    def generate_decoded_split(self, n: int, gen_stream: "torch.cuda.Stream") -> torch.Tensor:
-        """generate_decoded(n) in two parts, so the table of round r is generated while round r + 1 trains.
-
-        The prep graph (on the current stream, ~10 us) copies everything the generation reads from the live model
-        -- the bf16 / transposed weight copies of gen_weight_prep, each layer's bias, BatchNorm affine and running
-        statistics, the output bias -- and snapshots the RNG step counter, advancing the live one by the body's
-        bumps; the body graph (sampler, eval generator, decode) then runs on ``gen_stream`` reading only those
-        copies.  The table is bit-identical to generate_decoded(n), and training's random numbers are unchanged
-        (the live counter moves exactly as the unsplit pass would move it).  Returns a fresh tensor whose
-        producer is ``gen_stream``."""
-        self.generation_prep(n)
-        return self.generation_body(n, gen_stream)
-
-    def generation_prep(self, n: int) -> None:
-        """The prep half of generate_decoded_split(n), on the current stream (see there)."""
-        ent = self._gen_split.get(n) or self._capture_gen_split(n)
-        cur = torch.cuda.current_stream(self.device)
-        if self._gen_done is not None:          # the previous body still reads the snapshot
-            cur.wait_event(self._gen_done)
-        ent[0].replay()
-        self._gen_prepped = torch.cuda.Event()
-        self._gen_prepped.record(cur)
-
-    def generation_body(self, n: int, gen_stream: "torch.cuda.Stream") -> torch.Tensor:
-        """The body half, on ``gen_stream``: it waits for the prep (an event), not for whatever the current stream
-        queued since -- the body of round r may be issued after round r + 1's training."""
-        ent = self._gen_split[n]
-        gen_stream.wait_event(self._gen_prepped)
-        with torch.cuda.stream(gen_stream):
-            ent[1].replay()
-            out = ent[4].clone()
-            done = torch.cuda.Event()
-            done.record(gen_stream)
-        self._gen_done = done
-        if hasattr(self.ops, "check"):
-            self.ops.check()
-        return out
-
-    def _gen_snapshot(self):
-        if getattr(self, "_gsnap", None) is None:
-            names = [f"G.{i}.{k}" for i in range(len(self.gdims)) for k in ("b", "gamma", "beta", "rm", "rv")]
-            names.append("G.out.b")
-            self._gsnap = {nm: torch.empty_like(self.p[nm]) for nm in names}
-            self._gsnap_pairs = ([self._gsnap[nm] for nm in names], [self.p[nm] for nm in names])
-            self._gsnap_ctr = torch.zeros_like(self.ops.ctr)
-        return self._gsnap
-
-    def _gen_prep(self, n: int):
-        self._gen_weights16()
-        self._gen_snapshot()
-        torch._foreach_copy_(*self._gsnap_pairs)
-        self._gsnap_ctr.copy_(self.ops.ctr)
-        for _ in range(-(-n // self.cfg.gen_chunk)):     # the body's decode bumps, once per chunk
-            self.ops.L.rng_bump(self.ops.ctr)
-
-    def _gen_body(self, n: int, out: torch.Tensor, bufs):
-        w16 = (self._gw16, self._gwt)
-        for a in range(0, n, self.cfg.gen_chunk):
-            b = min(n, a + self.cfg.gen_chunk)
-            H, logits, col, opt = bufs(b - a)
-            self.ops.sample_gen(self.gen_cond, H, self.c_cols, self.z_cols, col_out=col, opt_out=opt, stream_id=21,
-                                ctr=self._gsnap_ctr)
-            self._g_forward16(H, logits, w16, (col, opt), params=self._gsnap)
-            self.ops.sample_decode(logits, out[a:b], self.gen_tables, stream_id=23, ctr=self._gsnap_ctr)
-
-    def _capture_gen_split(self, n: int):
-        from ..utils.devsync import CAPTURE_LOCK
-        m = min(n, self.cfg.gen_chunk)
-        H = self._gen_h16(m)
-        lg = _padded_rows(m, self.Dd, self.device)
-        col, opt = (torch.zeros(m, dtype=torch.int32, device=self.device) for _ in range(2))
-        out = torch.empty(n, len(self.gen_tables["cols"]), dtype=torch.float64, device=self.device)
-        bufs = lambda k: (H[:k], lg[:k], col[:k], opt[:k])  # noqa: E731
-        lane = self.ops.lane
-        with CAPTURE_LOCK:
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            # the body runs beside training: its own split-K / scratch slots (ops lane 7), never the step's
-            self.ops.lane = 7
-            try:
-                with torch.cuda.stream(s):      # warm-up (decode tables, lazy init); advances the RNG once
-                    self._gen_prep(n)
-                    self._gen_body(n, out, bufs)
-                torch.cuda.current_stream(self.device).wait_stream(s)
-                torch.cuda.synchronize(self.device)
-                gp, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gp, capture_error_mode=self.capture_mode):
-                    self._gen_prep(n)
-                with torch.cuda.graph(gb, capture_error_mode=self.capture_mode):
-                    self._gen_body(n, out, bufs)
-            finally:
-                self.ops.lane = lane
-        self._gen_split[n] = (gp, gb, H, lg, out, col, opt)
-        return self._gen_split[n]
-
-    def _gen_pass(self, n: int, out: torch.Tensor, bufs):
-        w16 = self._gen_weights16() if self.gen16 else None
-        for a in range(0, n, self.cfg.gen_chunk):
-            b = min(n, a + self.cfg.gen_chunk)
-            H, logits, col, opt = bufs(b - a)
-            self.ops.sample_gen(self.gen_cond, H, self.c_cols, self.z_cols, col_out=col, opt_out=opt, stream_id=21)
-            if w16 is None:
-                self._g_forward(H, logits, training=False, nhat=False, cond=(col, opt, True))
-            else:
-                self._g_forward16(H, logits, w16, (col, opt))
-            self.ops.sample_decode(logits, out[a:b], self.gen_tables, stream_id=23)
-
-    @property
-    def gen16(self) -> bool:
-        """Generation in bf16 storage (EngineConfig.gen_bf16): HIP bf16 backend, one-hot generator
-        GEMMs, and 8-aligned column offsets (16-B bf16 operand rows)."""
-        return (self.cfg.gen_bf16 and self.ops.name == "hip" and not getattr(self.ops, "f32", True) and
-                self.use_onehot and all(o % 8 == 0 for o in self.off))
-
-    def _gen_h16(self, rows: int) -> torch.Tensor:
-        """bf16 generator activations [rows, ceil8(c0)]: [out_{L-1} | ... | out_0 | z] (no one-hot block)."""
-        return torch.zeros(rows, -(-self.c_cols[0] // 8) * 8, dtype=torch.bfloat16, device=self.device)
-
-    def _gen_weights16(self):
-        """Generation views of the generator weights, refreshed from the current fp32 weights inside
-        the generation graph (every replay sees the aggregated model), in ONE launch: per layer the
-        bf16 copy of the dense columns and the one-hot block transposed to [C, N] fp32.
-        Returns (bf16 copies, transposed blocks), one per layer (G-out last)."""
-        c0 = self.c_cols[0]
-        names = [f"G.{i}.W" for i in range(len(self.gdims))] + ["G.out.W"]
-        starts = list(self.off[:len(self.gdims)]) + [0]
-        if getattr(self, "_gw16", None) is None:
-            self._gw16 = [torch.zeros(self.p[nm].shape[0], -(-(c0 - a) // 8) * 8, dtype=torch.bfloat16,
-                                      device=self.device) for nm, a in zip(names, starts)]
-            self._gwt = [torch.zeros(self.p[nm].shape[1] - (c0 - a), self.p[nm].shape[0], device=self.device)
-                         for nm, a in zip(names, starts)]
-        self.ops.L.gen_weight_prep([self.p[nm] for nm in names], [c0 - a for a in starts], self._gw16, self._gwt)
-        return self._gw16, self._gwt
-
-    def _g_forward16(self, H16, logits, w16, cond, params=None):
-        """Eval-mode generator on the bf16 buffer: each layer's GEMM reads bf16 rows and weights,
-        gathers the one-hot block from col / opt, and writes bf16 (BN-eval + ReLU epilogue); the output
-        layer writes fp32 logits.  w16 = _gen_weights16(); params: biases / BN tensors by name (default the
-        live ones; the pipelined generation passes its snapshot)."""
-        o, p = self.ops, (self.p if params is None else params)
-        c0 = self.c_cols[0]
-        col, opt = cond
-        wd, wt = w16
-        for i, g in enumerate(self.gdims):
-            a, b_ = self.off[i], self.off[i + 1]
-            oh = (wt[i], col, opt, self._cond_off, True)
-            o.linear_bn_relu(H16[:, a:c0], wd[i], p[f"G.{i}.b"], p[f"G.{i}.gamma"], p[f"G.{i}.beta"], H16[:, b_:a],
-                             None, None, None, None, p[f"G.{i}.rm"], p[f"G.{i}.rv"], False, self.cfg.bn_momentum,
-                             self.cfg.bn_eps, onehot=oh)
-        oh = (wt[-1], col, opt, self._cond_off, True)
-        o.gemm(H16[:, :c0], wd[-1], logits, tb=True, bias=p["G.out.b"], onehot=oh)
-
-    def _capture_gen(self, n: int):
-        """Capture generate_decoded(n) with its own static buffers (graphs hold no tensor refs)."""
-        from ..utils.devsync import CAPTURE_LOCK
-        m = min(n, self.cfg.gen_chunk)
-        H = self._gen_h16(m) if self.gen16 else _padded_rows(m, self.Hw, self.device)
-        lg = _padded_rows(m, self.Dd, self.device)
-        col, opt = (torch.zeros(m, dtype=torch.int32, device=self.device) for _ in range(2))
-        out = torch.empty(n, len(self.gen_tables["cols"]), dtype=torch.float64, device=self.device)
-        bufs = lambda k: (H[:k], lg[:k], col[:k], opt[:k])  # noqa: E731
-        with CAPTURE_LOCK:
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):      # warm-up (decode tables, lazy init); advances the RNG once
-                self._gen_pass(n, out, bufs)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=self.capture_mode):
-                self._gen_pass(n, out, bufs)
-        self._gen_graphs[n] = (g, H, lg, out, col, opt)
-        return self._gen_graphs[n]
-
-    def _gen_buffers(self, n: int, bf16: bool | None = None):
-        bf16 = self.gen16 if bf16 is None else bf16
-        if self._gen_bufs is None or self._gen_bufs[0].shape[0] < n or \
-                (self._gen_bufs[0].dtype == torch.bfloat16) != bf16:
-            m = max(n, min(self.cfg.gen_chunk, n))
-            H = self._gen_h16(m) if bf16 else _padded_rows(m, self.Hw, self.device)
-            self._gen_bufs = (H, _padded_rows(m, self.Dd, self.device),
-                              torch.zeros(m, dtype=torch.int32, device=self.device),
-                              torch.zeros(m, dtype=torch.int32, device=self.device))
-        H, lg, col, opt = self._gen_bufs
-        return H[:n], lg[:n], col[:n], opt[:n]

@@ -14,6 +14,33 @@ import torch
 CAPTURE_LOCK = threading.RLock()
 
 
+def warm_and_capture(device, warm, bodies, *, snapshot=None, restore=None, mode="global"):
+    """Run ``warm()`` eagerly on a side stream (allocator, lazy init), then capture each callable of ``bodies`` into a
+    hipGraph of its own, in order; returns the graphs.  ``snapshot()`` is enqueued BEFORE the side stream forks from
+    the current one, so the warm-up cannot overtake its copies; ``restore(what it returned)`` runs once the device is
+    idle again, also when the warm-up raised part-way.  Without them what the warm-up changed stays changed.  The
+    captures see the restored state (``torch.cuda.graph`` synchronises on entry).  ``mode``: ``thread_local`` when
+    several engines capture from threads."""
+    with CAPTURE_LOCK:          # no device-wide sync from another client thread meanwhile
+        cur = torch.cuda.current_stream(device)
+        saved = snapshot() if snapshot is not None else None
+        s = torch.cuda.Stream(device)
+        s.wait_stream(cur)
+        try:
+            with torch.cuda.stream(s):
+                warm()
+        finally:
+            cur.wait_stream(s)
+            torch.cuda.synchronize(device)
+            if restore is not None:
+                restore(saved)
+        graphs = [torch.cuda.CUDAGraph() for _ in bodies]
+        for g, body in zip(graphs, bodies):
+            with torch.cuda.graph(g, capture_error_mode=mode):
+                body()
+        return graphs
+
+
 def device_sync(device) -> None:
     if device is None or getattr(device, "type", "") != "cuda":
         return

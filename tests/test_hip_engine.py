@@ -276,6 +276,35 @@ def test_bf16_generation_is_bit_identical(n):
     eng.cfg.gen_bf16 = True
 
 
+def test_split_generation_matches_unsplit_over_chunks():
+    """generate_decoded_split(n) -- prep graph on the current stream, body graph on a side stream -- gives
+    generate_decoded(n)'s table bit for bit from the same RNG counter and leaves the counter where the unsplit pass
+    leaves it: one full chunk, a ragged second chunk, three chunks with a ragged last.  Each size twice: the first
+    calls capture their graphs (warm-up pass included), the second only replay."""
+    from fed_tgan_amd.models.samplers import CondTables
+    from fed_tgan_amd.ops import native
+    native.require()
+    _, _, _, _, _, _, tr, X = small_table()
+    eng = CTGANEngine(tr.layout, EngineConfig(batch_size=200, gen_chunk=64), DEV, backend="hip", seed=11)
+    eng.set_training_data(X)
+    eng.set_generation_tables(CondTables.from_encoded(X, tr.layout), tr)
+    assert eng.gen16 and eng.can_split_generation()
+    side = torch.cuda.Stream(DEV)
+    ctr0 = eng.ops.ctr.clone()
+    for n in (64, 77, 150):
+        for _ in range(2):
+            eng.ops.ctr.copy_(ctr0)
+            a = eng.generate_decoded(n)
+            torch.cuda.synchronize()
+            ctr_a = eng.ops.ctr.clone()
+            eng.ops.ctr.copy_(ctr0)
+            b = eng.generate_decoded_split(n, side)
+            torch.cuda.synchronize()
+            assert a.shape == (n, len(tr.meta)) and torch.equal(a, b), n
+            assert torch.equal(eng.ops.ctr, ctr_a) and not torch.equal(ctr_a, ctr0), n
+    eng.release()
+
+
 def test_input_major_generator_weights_match_row_major():
     """EngineConfig.g_wt: the generator weights stored input-major ([in, out] rows; transposed views
     into the GEMMs, one-hot gathers from contiguous rows) train like the [out, in] layout from the same

@@ -73,7 +73,7 @@ def main():
                 for k in range(int(lay.cond_width[c])):
                     W[int(lay.cond_start[c]) + k, W.shape[1] - lay.n_opt + int(lay.cond_offset[c]) + k] = 60.0
     eng.generate_decoded(m)
-    plain = eng._gen_graphs[m][0]
+    plain = eng._gen_graphs[m].graph
     common = str(counts.index[0])
     req = build_request(tr, meta, vocabs, {"class": common}, m, dev)
     eng.generate_decoded_where(m, req, chunk=m, max_passes=64)

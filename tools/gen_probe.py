@@ -39,7 +39,8 @@ def main():
         eng.cfg.gen_bf16 = bf16
         eng._gen_graphs, eng._gen_bufs = {}, None
         eng.generate_decoded(n)
-        _, H, lg, out, col, opt = eng._gen_graphs[n]
+        ent = eng._gen_graphs[n]
+        H, lg, out, col, opt = ent.H, ent.logits, ent.out, ent.col, ent.opt
         w16 = eng._gen_weights16()[0] if bf16 else None
         res = []
         for i, g in enumerate(eng.gdims):
@@ -75,7 +76,8 @@ def main():
         # G0 variants: what does its time depend on (one-hot gather, BN epilogue, output dtype, tile)?
         from fed_tgan_amd.ops.hip import EPI_BN_EVAL_RELU
         layers_for(True)
-        _, H, lg, out, col, opt = eng._gen_graphs[n]
+        ent = eng._gen_graphs[n]
+        H, lg, out, col, opt = ent.H, ent.logits, ent.out, ent.col, ent.opt
         w16 = eng._gen_weights16()[0]
         a, b_ = eng.off[0], eng.off[1]
         W = p["G.0.W"]
