@@ -2007,6 +2007,57 @@ __device__ __forceinline__ void bn_colsum(float (&v)[NV], float* sh) {
   __syncthreads();
 }
 
+// The arithmetic of training BatchNorm in one place.  Contraction is pinned: each product below is fused into an fma
+// exactly where it is written as one (the forms the register-resident kernel has always been compiled to) and
+// nowhere else, so a kernel that reuses these helpers on the same rows in the same order rounds alike.
+struct BnStat {
+  float mu, var, is;   // batch mean, biased batch variance, 1 / sqrt(var + eps)
+};
+
+// every load of a BN workgroup (rows, shifts, column parameters) is requested above this line and consumed below
+// it: the rows' round trips overlap instead of queueing behind the arithmetic on the first ones
+__device__ __forceinline__ void bn_loads_issued() { __builtin_amdgcn_sched_barrier(0); }
+
+__device__ __forceinline__ float bn_sq(float d) {
+#pragma clang fp contract(off)
+  return d * d;
+}
+
+// one row's d = x - shift into the running sum(d), sum(d^2): two plain adds (the square is rounded on its own)
+__device__ __forceinline__ void bn_acc(float& s, float& s2, float d) {
+  s += d;
+  s2 += bn_sq(d);
+}
+
+__device__ __forceinline__ BnStat bn_stat(float s, float s2, float shift, int rpg, float eps) {
+#pragma clang fp contract(off)
+  BnStat st;
+  const float m = s / (float)rpg;
+  st.mu = shift + m;
+  st.var = fmaxf(__builtin_fmaf(-m, m, s2 / (float)rpg), 0.f);
+  st.is = rsqrtf(st.var + eps);
+  return st;
+}
+
+// one batch's update of the running mean / (unbiased) variance
+__device__ __forceinline__ void bn_ema(float& m, float& v, const BnStat& st, float momentum, float unb) {
+#pragma clang fp contract(off)
+  m = __builtin_fmaf(1.f - momentum, m, momentum * st.mu);
+  v = __builtin_fmaf(1.f - momentum, v, momentum * st.var * unb);
+}
+
+__device__ __forceinline__ float bn_unbias(int rpg) { return (float)rpg / (float)max(rpg - 1, 1); }
+
+__device__ __forceinline__ float bn_nhat(float x, const BnStat& st) {
+#pragma clang fp contract(off)
+  return (x - st.mu) * st.is;
+}
+
+__device__ __forceinline__ float bn_affine_relu(float n, float gm, float bt) {
+  const float y = __builtin_fmaf(n, gm, bt);
+  return y > 0.f ? y : 0.f;
+}
+
 template <int COLS, int MAXR, bool BT_ = false, int NTH = BN_THREADS>
 __global__ __launch_bounds__(NTH) void bn_relu_train_kernel(
     const float* __restrict__ a, int lda, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -2044,32 +2095,28 @@ __global__ __launch_bounds__(NTH) void bn_relu_train_kernel(
   float x[MAXR];
   float s[2 * BN_MAXG] = {0.f, 0.f, 0.f, 0.f};   // sum d (batch 0, 1), sum d^2 (batch 0, 1)
 #pragma unroll
+  for (int i = 0; i < MAXR; ++i) x[i] = a[(size_t)min(grp + i * GROUPS, rows - 1) * lda + cc];
+  bn_loads_issued();
+#pragma unroll
   for (int i = 0; i < MAXR; ++i) {
     const int r = grp + i * GROUPS;
-    const float v = a[(size_t)min(r, rows - 1) * lda + cc];
-    x[i] = v;
     const bool g1 = r >= rpg;
-    const float d = (r < rows) ? v - (g1 ? sh1 : sh0) : 0.f;
-    if (g1) { s[1] += d; s[3] += d * d; } else { s[0] += d; s[2] += d * d; }
+    const float dv = x[i] - (g1 ? sh1 : sh0);
+    const float d = (r < rows) ? dv : 0.f;
+    if (g1) bn_acc(s[1], s[3], d); else bn_acc(s[0], s[2], d);
   }
   bn_colsum<COLS, 2 * BN_MAXG, NTH>(s, sh);
-  const float m0 = s[0] / (float)rpg, m1 = s[1] / (float)rpg;
-  const float mu0 = sh0 + m0, mu1 = sh1 + m1;
-  const float var0 = fmaxf(s[2] / (float)rpg - m0 * m0, 0.f);   // biased batch variances
-  const float var1 = fmaxf(s[3] / (float)rpg - m1 * m1, 0.f);
-  const float is0 = rsqrtf(var0 + eps), is1 = rsqrtf(var1 + eps);
+  const BnStat st0 = bn_stat(s[0], s[2], sh0, rpg, eps), st1 = bn_stat(s[1], s[3], sh1, rpg, eps);
   if (grp == 0 && ok) {
-    const float unb = (float)rpg / (float)max(rpg - 1, 1);
+    const float unb = bn_unbias(rpg);
     float m = rm0, v = rv0;
-    mean[c] = mu0;
-    invstd[c] = is0;
-    m = (1.f - momentum) * m + momentum * mu0;          // batch after batch, in row order
-    v = (1.f - momentum) * v + momentum * var0 * unb;
+    mean[c] = st0.mu;
+    invstd[c] = st0.is;
+    bn_ema(m, v, st0, momentum, unb);          // batch after batch, in row order
     if (groups > 1) {
-      mean[(size_t)cols + c] = mu1;
-      invstd[(size_t)cols + c] = is1;
-      m = (1.f - momentum) * m + momentum * mu1;
-      v = (1.f - momentum) * v + momentum * var1 * unb;
+      mean[(size_t)cols + c] = st1.mu;
+      invstd[(size_t)cols + c] = st1.is;
+      bn_ema(m, v, st1, momentum, unb);
     }
     rm[c] = m;
     rv[c] = v;
@@ -2079,11 +2126,9 @@ __global__ __launch_bounds__(NTH) void bn_relu_train_kernel(
   for (int i = 0; i < MAXR; ++i) {
     const int r = grp + i * GROUPS;
     if (r < rows) {
-      const bool g1 = r >= rpg;
-      const float n = (x[i] - (g1 ? mu1 : mu0)) * (g1 ? is1 : is0);
+      const float n = bn_nhat(x[i], r >= rpg ? st1 : st0);
       nhat[(size_t)r * ldn + c] = n;
-      const float y = n * gm + bt;
-      out[(size_t)r * ldo + c] = y > 0.f ? y : 0.f;
+      out[(size_t)r * ldo + c] = bn_affine_relu(n, gm, bt);
     }
   }
 }
