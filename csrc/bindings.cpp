@@ -1292,6 +1292,146 @@ int64_t nn_chunks(int64_t nr) { return fedtgan::nn_chunks(nr); }
 int64_t nn_scratch(int64_t nq, int64_t nr) { return fedtgan::nn_scratch_doubles(nq, nr); }
 int64_t nn_stats_part(int64_t n) { return 2 * (int64_t)fedtgan::nn_stats_blocks(n); }
 
+// ----------------------------------------------------------------------------- correlation evaluator
+namespace {
+bool corr_i64(const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(); }
+}  // namespace
+
+void corr_pack(const Tensor& values, const Tensor& kind, const Tensor& slot, const Tensor& card, const Tensor& cont,
+               const Tensor& cat_t, const Tensor& mean, const Tensor& part) {
+  TORCH_CHECK(sim_f64(values) && values.dim() == 2 && values.size(0) >= 1 && values.size(1) >= 1,
+              "corr_pack: values must be contiguous float64 [rows >= 1, n_cols]");
+  TORCH_CHECK(values.numel() < (int64_t)INT32_MAX, "corr_pack: a table holds fewer than 2^31 values");
+  const int64_t rows = values.size(0);
+  TORCH_CHECK(sim_i32(kind) && sim_i32(slot) && kind.numel() == values.size(1) && slot.numel() == values.size(1),
+              "corr_pack: int32 kind / slot, one entry per column");
+  TORCH_CHECK(sim_f64(cont) && cont.dim() == 2 && cont.size(0) >= rows && sim_i32(cat_t) && cat_t.dim() == 2 &&
+                  cat_t.size(1) >= rows, "corr_pack: cont float64 [>= rows, n_cont], cat_t int32 [n_cat, >= rows]");
+  TORCH_CHECK(cont.size(1) + cat_t.size(0) == values.size(1), "corr_pack: n_cont + n_cat must be n_cols");
+  TORCH_CHECK(sim_i32(card) && card.numel() == cat_t.size(0) && sim_f64(mean) && mean.numel() == cont.size(1),
+              "corr_pack: card int32 [n_cat], mean float64 [n_cont]");
+  const int64_t chunks = (rows + fedtgan::CORR_CHUNK - 1) / fedtgan::CORR_CHUNK;
+  TORCH_CHECK(sim_f64(part) && part.numel() >= chunks * cont.size(1), "corr_pack: part needs ", chunks * cont.size(1),
+              " float64");
+  fedtgan::CorrPackArgs a{};
+  a.values = values.data_ptr<double>();
+  a.rows = (int)rows;
+  a.n_cols = (int)values.size(1);
+  a.kind = kind.data_ptr<int>();
+  a.slot = slot.data_ptr<int>();
+  a.n_cont = (int)cont.size(1);
+  a.n_cat = (int)cat_t.size(0);
+  a.card = a.n_cat ? card.data_ptr<int>() : nullptr;
+  a.cont = a.n_cont ? cont.data_ptr<double>() : nullptr;
+  a.cat_t = a.n_cat ? cat_t.data_ptr<int>() : nullptr;
+  a.ldk = cat_t.size(1);
+  a.mean = a.n_cont ? mean.data_ptr<double>() : nullptr;
+  a.part = part.data_ptr<double>();
+  fedtgan::launch_corr_pack(a, cur_stream());
+}
+
+void corr_moments(const Tensor& cont, const Tensor& cat_t, int64_t n, const Tensor& mean, const Tensor& card,
+                  const Tensor& offs, const Tensor& G, const Tensor& part) {
+  TORCH_CHECK(sim_f64(cont) && cont.dim() == 2 && sim_i32(cat_t) && cat_t.dim() == 2 && n >= 1 && cont.size(0) >= n &&
+                  cat_t.size(1) >= n && n < (int64_t)INT32_MAX,
+              "corr_moments: cont float64 [>= n, n_cont], cat_t int32 [n_cat, >= n]");
+  const int64_t n_cont = cont.size(1), n_cat = cat_t.size(0);
+  TORCH_CHECK(sim_f64(mean) && mean.numel() == n_cont && sim_i32(card) && card.numel() == n_cat && sim_i32(offs) &&
+                  offs.numel() == n_cat + 1, "corr_moments: mean [n_cont], card [n_cat], offs [n_cat + 1]");
+  TORCH_CHECK(sim_f64(G) && G.dim() == 2 && G.size(1) == n_cont && G.size(0) >= n_cont,
+              "corr_moments: G float64 [W, n_cont]");
+  const int64_t W = G.size(0);
+  TORCH_CHECK(W < (int64_t)INT32_MAX && W * n_cont < (int64_t)INT32_MAX, "corr_moments: G too large");
+  const fedtgan::CorrGroups gr = fedtgan::corr_groups(n, W, n_cont);
+  TORCH_CHECK(sim_f64(part) && part.numel() >= (int64_t)gr.groups * W * n_cont, "corr_moments: part needs ",
+              (int64_t)gr.groups * W * n_cont, " float64");
+  if (n_cont == 0) return;
+  fedtgan::CorrMomentsArgs a{};
+  a.cont = cont.data_ptr<double>();
+  a.cat_t = n_cat ? cat_t.data_ptr<int>() : nullptr;
+  a.ldk = cat_t.size(1);
+  a.n = (int)n;
+  a.n_cont = (int)n_cont;
+  a.n_cat = (int)n_cat;
+  a.W = (int)W;
+  a.mean = mean.data_ptr<double>();
+  a.card = n_cat ? card.data_ptr<int>() : nullptr;
+  a.offs = offs.data_ptr<int>();
+  a.G = G.data_ptr<double>();
+  a.part = part.data_ptr<double>();
+  fedtgan::launch_corr_moments(a, cur_stream());
+}
+
+void corr_counts(const Tensor& cat_t, int64_t n, const Tensor& pairs, const Tensor& poff, const Tensor& counts,
+                 int64_t lds_bins) {
+  TORCH_CHECK(sim_i32(cat_t) && cat_t.dim() == 2 && n >= 1 && cat_t.size(1) >= n && n < (int64_t)INT32_MAX,
+              "corr_counts: cat_t int32 [n_cat, >= n]");
+  TORCH_CHECK(sim_i32(pairs) && pairs.dim() == 2 && pairs.size(1) == 4 && corr_i64(poff) &&
+                  poff.numel() == pairs.size(0) + 1 && pairs.size(0) < (int64_t)INT32_MAX,
+              "corr_counts: pairs int32 [P, 4], poff int64 [P + 1]");
+  TORCH_CHECK(sim_i32(counts) && lds_bins >= 1 && lds_bins <= fedtgan::CORR_LDS_BINS,
+              "corr_counts: counts int32, lds_bins in 1..CORR_LDS_BINS");
+  fedtgan::CorrCountsArgs a{};
+  a.cat_t = cat_t.data_ptr<int>();
+  a.ldk = cat_t.size(1);
+  a.n = (int)n;
+  a.n_cat = (int)cat_t.size(0);
+  a.n_pairs = (int)pairs.size(0);
+  a.pairs = pairs.data_ptr<int>();
+  a.poff = poff.data_ptr<int64_t>();
+  a.counts = counts.data_ptr<int>();
+  a.total = counts.numel();
+  a.lds_bins = (int)lds_bins;
+  fedtgan::launch_corr_counts(a, cur_stream());
+}
+
+void corr_matrix(const Tensor& G, const Tensor& counts, const Tensor& poff, const Tensor& kind, const Tensor& slot,
+                 const Tensor& card, const Tensor& offs, int64_t n, const Tensor& A) {
+  TORCH_CHECK(sim_f64(A) && A.dim() == 2 && A.size(0) == A.size(1) && A.size(0) >= 1, "corr_matrix: A float64 [C, C]");
+  const int64_t C = A.size(0);
+  TORCH_CHECK(sim_i32(kind) && sim_i32(slot) && kind.numel() == C && slot.numel() == C,
+              "corr_matrix: int32 kind / slot, one entry per column");
+  const int64_t n_cat = card.numel(), n_cont = C - n_cat;
+  TORCH_CHECK(sim_i32(card) && sim_i32(offs) && n_cont >= 0 && offs.numel() == n_cat + 1,
+              "corr_matrix: card int32 [n_cat], offs int32 [n_cat + 1]");
+  // (G must also cover n_cont + offs[n_cat] rows; offs lives on the device, so the kernel checks that per entry)
+  TORCH_CHECK(sim_f64(G) && G.dim() == 2 && G.size(1) == n_cont && G.size(0) >= n_cont,
+              "corr_matrix: G float64 [W >= n_cont, n_cont]");
+  TORCH_CHECK(sim_i32(counts) && corr_i64(poff) && poff.numel() == 1 + n_cat + n_cat * (n_cat - 1) / 2,
+              "corr_matrix: counts int32, poff int64 [1 + n_cat + n_cat (n_cat - 1) / 2]");
+  TORCH_CHECK(n >= 1 && n < (int64_t)INT32_MAX, "corr_matrix: n");
+  fedtgan::CorrMatrixArgs a{};
+  a.G = G.data_ptr<double>();
+  a.counts = counts.data_ptr<int>();
+  a.poff = poff.data_ptr<int64_t>();
+  a.total = counts.numel();
+  a.n_pairs = (int)poff.numel() - 1;
+  a.kind = kind.data_ptr<int>();
+  a.slot = slot.data_ptr<int>();
+  a.card = n_cat ? card.data_ptr<int>() : nullptr;
+  a.offs = offs.data_ptr<int>();
+  a.n = (int)n;
+  a.C = (int)C;
+  a.n_cont = (int)n_cont;
+  a.n_cat = (int)n_cat;
+  a.W = (int)G.size(0);
+  a.A = A.data_ptr<double>();
+  fedtgan::launch_corr_matrix(a, cur_stream());
+}
+
+void corr_diff(const Tensor& A, const Tensor& B, const Tensor& out) {
+  TORCH_CHECK(sim_f64(A) && sim_f64(B) && A.dim() == 2 && A.size(0) == A.size(1) && A.size(0) >= 1 && B.dim() == 2 &&
+                  B.size(0) == A.size(0) && B.size(1) == A.size(0), "corr_diff: two float64 [C, C] matrices");
+  TORCH_CHECK(sim_f64(out) && out.numel() >= 3, "corr_diff: out float64 [>= 3]");
+  fedtgan::launch_corr_diff(A.data_ptr<double>(), B.data_ptr<double>(), (int)A.size(0), out.data_ptr<double>(),
+                            cur_stream());
+}
+
+int64_t corr_chunk() { return fedtgan::CORR_CHUNK; }
+int64_t corr_lds_bins() { return fedtgan::CORR_LDS_BINS; }
+int64_t corr_part(int64_t n_max, int64_t W, int64_t n_cont) { return fedtgan::corr_part_doubles(n_max, W, n_cont); }
+int64_t corr_groups(int64_t n, int64_t W, int64_t n_cont) { return fedtgan::corr_groups(n, W, n_cont).groups; }
+
 // ----------------------------------------------------------------------------- native RCCL plane (csrc/comm)
 void rccl_load_op(const std::string& path) { fedtgan::comm::rccl_load(path); }
 
@@ -1618,6 +1758,12 @@ int64_t set_tuning(const std::string& key, int64_t value) {
   if (key == "vgm_split_of") {   // read-only probe: the split a fit of `value` columns x 40000 rows would use
     return fedtgan::vgm_fit_split((int)value, 40000);
   }
+  if (key == "corr_part_target") {   // fp64 partials corr_moments' row groups may fill (kernels/launch.h); 0 = default
+    TORCH_CHECK(value >= 0, "corr_part_target: >= 0");
+    const int64_t prev = fedtgan::g_corr_part_target;
+    fedtgan::g_corr_part_target = value ? value : fedtgan::CORR_PART_TARGET;
+    return prev;
+  }
   if (key == "adam_max_blocks") {
     TORCH_CHECK(value >= 1 && value <= 65535, "adam_max_blocks: 1..65535");
     const int64_t prev = fedtgan::g_adam_max_blocks;
@@ -1769,6 +1915,21 @@ TORCH_LIBRARY(fedtgan, m) {
   m.def("nn_scratch(int nq, int nr) -> int", &nn_scratch);
   m.def("nn_stats_part(int n) -> int", &nn_stats_part);
   m.def(
+      "corr_pack(Tensor values, Tensor kind, Tensor slot, Tensor card, Tensor(a!) cont, Tensor(b!) cat_t, "
+      "Tensor(c!) mean, Tensor(d!) part) -> ()");
+  m.def(
+      "corr_moments(Tensor cont, Tensor cat_t, int n, Tensor mean, Tensor card, Tensor offs, Tensor(a!) G, "
+      "Tensor(b!) part) -> ()");
+  m.def("corr_counts(Tensor cat_t, int n, Tensor pairs, Tensor poff, Tensor(a!) counts, int lds_bins) -> ()");
+  m.def(
+      "corr_matrix(Tensor G, Tensor counts, Tensor poff, Tensor kind, Tensor slot, Tensor card, Tensor offs, int n, "
+      "Tensor(a!) A) -> ()");
+  m.def("corr_diff(Tensor A, Tensor B, Tensor(a!) out) -> ()");
+  m.def("corr_chunk() -> int", &corr_chunk);
+  m.def("corr_lds_bins() -> int", &corr_lds_bins);
+  m.def("corr_part(int n_max, int W, int n_cont) -> int", &corr_part);
+  m.def("corr_groups(int n, int W, int n_cont) -> int", &corr_groups);
+  m.def(
       "vgm_estep(Tensor x, Tensor n_rows, Tensor consts, Tensor means, Tensor prec, Tensor(a!) partial, "
       "int rows_per_block) -> ()");
   m.def("kmeans_step(Tensor x, Tensor n_rows, Tensor centers, Tensor(a!) partial, int rows_per_block) -> ()");
@@ -1832,6 +1993,11 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("nn_top2", &nn_top2);
   m.impl("nn_stats", &nn_stats);
   m.impl("nn_percentiles", &nn_percentiles);
+  m.impl("corr_pack", &corr_pack);
+  m.impl("corr_moments", &corr_moments);
+  m.impl("corr_counts", &corr_counts);
+  m.impl("corr_matrix", &corr_matrix);
+  m.impl("corr_diff", &corr_diff);
   m.impl("vgm_encode", &vgm_encode);
   m.impl("vgm_estep", &vgm_estep);
   m.impl("kmeans_step", &kmeans_step);

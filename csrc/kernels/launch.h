@@ -543,6 +543,80 @@ void launch_nn_stats(const double* d1, const double* d2, int n, double* keys, in
 // out[0..3] = 5th percentile of each (ascending) key row, smallest sqrt(d1), share of rows with d1 == 0
 void launch_nn_percentiles(const double* keys, int64_t ld, int n, const double* part, double* out, hipStream_t stream);
 
+// Correlation evaluator (kernels/correlation.hip): the [C, C] association matrix of a decoded table (Pearson r,
+// Theil's U, correlation ratio) and its distance to the real table's.  Every fp64 sum has a fixed order, counting
+// is in integers; no floating-point atomics, no allocation, no host round trip.
+constexpr int CORR_CHUNK = 1024;            // rows per chunk; a workgroup sums a whole number of consecutive chunks
+constexpr int CORR_COL_TILE = 64;           // continuous columns per workgroup of the column sums
+constexpr int CORR_COUNT_ROWS = 8192;       // rows per workgroup of the contingency count
+// int32 bins of a contingency table counted in LDS: 64 KiB, so two workgroups share a CU's 160 KiB with room to
+// spare; a pair with more bins counts in its global table directly
+constexpr int CORR_LDS_BINS = 16384;
+constexpr int64_t CORR_PART_TARGET = 8ll << 20;   // fp64 partials (64 MiB) the row groups of corr_moments may fill
+extern int64_t g_corr_part_target;                // set_tuning("corr_part_target"): the same, adjustable (tests)
+enum CorrKind : int { CORR_CONT = 0, CORR_CAT = 1 };
+struct CorrGroups {
+  int groups;            // row groups: one partial each
+  int rows;              // rows per group, a multiple of CORR_CHUNK
+};
+// the row split of a table of n rows with one-hot width W and n_cont continuous columns (a function of the shape
+// alone, so a shape always sums in the same order)
+CorrGroups corr_groups(int64_t n, int64_t W, int64_t n_cont);
+int64_t corr_part_doubles(int64_t n_max, int64_t W, int64_t n_cont);   // what any n <= n_max needs
+struct CorrPackArgs {
+  const double* values;   // [rows, n_cols] decoded table, row-major
+  int rows, n_cols;
+  const int* kind;        // [n_cols] CorrKind
+  const int* slot;        // [n_cols] column of cont / row of cat_t
+  const int* card;        // [n_cat] K_c: codes lie in [0, K_c), anything else lands in the overflow bin K_c
+  double* cont;           // [>= rows, n_cont] the continuous columns, row-major
+  int* cat_t;             // [n_cat, ldk] codes, one row per column
+  int64_t ldk;
+  double* mean;           // [n_cont]
+  double* part;           // scratch: one sum per (CORR_CHUNK rows, continuous column)
+  int n_cont, n_cat;
+};
+void launch_corr_pack(const CorrPackArgs& a, hipStream_t stream);
+struct CorrMomentsArgs {
+  const double* cont;     // [>= n, n_cont]
+  const int* cat_t;       // [n_cat, ldk]
+  int64_t ldk;
+  int n, n_cont, n_cat, W;
+  const double* mean;     // [n_cont]
+  const int* card;        // [n_cat]
+  const int* offs;        // [n_cat + 1] first one-hot row of a column, less n_cont; offs[n_cat] = W - n_cont
+  double* G;              // [W, n_cont] = F^T Xc with F = [Xc | one-hot(codes)]
+  double* part;           // [groups, W, n_cont]
+};
+void launch_corr_moments(const CorrMomentsArgs& a, hipStream_t stream);
+struct CorrCountsArgs {
+  const int* cat_t;       // [n_cat, ldk]
+  int64_t ldk;
+  int n, n_cat, n_pairs;
+  const int* pairs;       // [n_pairs, 4]: column a, column b (-1: the margin of a), bins of a, bins of b
+  const int64_t* poff;    // [n_pairs + 1] first bin of a pair's table in counts
+  int* counts;            // [total] int32 tables, row-major [bins of a][bins of b]
+  int64_t total;
+  int lds_bins;           // the largest table counted in LDS (<= CORR_LDS_BINS)
+};
+void launch_corr_counts(const CorrCountsArgs& a, hipStream_t stream);
+struct CorrMatrixArgs {
+  const double* G;        // [W, n_cont]
+  const int* counts;
+  const int64_t* poff;    // [n_pairs + 1]: margins of the n_cat columns first, then the pairs a < b in row-major order
+  int64_t total;
+  int n_pairs;
+  const int* kind;        // [C]
+  const int* slot;        // [C]
+  const int* card;        // [n_cat]
+  const int* offs;        // [n_cat + 1]
+  int n, C, n_cont, n_cat, W;
+  double* A;              // [C, C]
+};
+void launch_corr_matrix(const CorrMatrixArgs& a, hipStream_t stream);
+// out[0] = ||A - B||_F, out[1] = mean |A - B| over the off-diagonal entries (0 for C == 1), out[2] = their maximum
+void launch_corr_diff(const double* A, const double* B, int C, double* out, hipStream_t stream);
+
 struct GenWeightJob {
   const float* w;   // fp32 weight, element (n, k) at w[n * ldw + k * skw] (skw = 1: [N, K] rows; ldw = 1: input-major storage)
   int N, ldw, skw, kd, C;

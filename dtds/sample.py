@@ -33,6 +33,10 @@ def main(argv=None):
     p.add_argument("-privacy_against", default=None, metavar="REAL.csv",
                    help="also print one JSON line with DCR / NNDR of the generated rows against this table (5th "
                         "percentiles, minimum, share of exact copies, and the real table's own baseline)")
+    p.add_argument("-corr_against", default=None, metavar="REAL.csv",
+                   help="also print one JSON line with Diff. Corr. of the generated rows against this table (the "
+                        "distance between the two tables' association matrices, its mean and maximum per column "
+                        "pair, and the real table's own even / odd row baseline)")
     args = p.parse_args(argv)
     import torch
     from fed_tgan_amd.models.conditional import parse_where
@@ -42,11 +46,11 @@ def main(argv=None):
     gen = load_generator(args.model, dev, backend=args.backend, seed=args.seed)
     out = args.out or f"{gen.name}_synthetic.csv"
     t0 = time.time()
-    scores = privacy = None
-    if args.score_against or args.privacy_against:
-        scores, privacy = gen.write_csv_evaluated(out, args.n, score_real=args.score_against,
-                                                  privacy_real=args.privacy_against, where=where or None,
-                                                  max_passes=args.max_passes)
+    scores = privacy = corr = None
+    if args.score_against or args.privacy_against or args.corr_against:
+        scores, privacy, corr = gen.write_csv_all(out, args.n, score_real=args.score_against,
+                                                  privacy_real=args.privacy_against, corr_real=args.corr_against,
+                                                  where=where or None, max_passes=args.max_passes)
     else:
         gen.write_csv(out, args.n, where=where or None, max_passes=args.max_passes)
     cond = ""
@@ -58,6 +62,8 @@ def main(argv=None):
         print(f"Avg_JSD {scores[0]!r} Avg_WD {scores[1]!r} (against {args.score_against})", flush=True)
     if privacy is not None:
         print(json.dumps(privacy), flush=True)
+    if corr is not None:
+        print(json.dumps(corr), flush=True)
     return out
 
 

@@ -1,1 +1,2 @@
+from .correlation import CorrelationScores, DeviceCorrelation  # noqa: F401
 from .privacy import DevicePrivacy, PrivacyScores  # noqa: F401

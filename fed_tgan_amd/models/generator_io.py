@@ -60,6 +60,7 @@ class LoadedGenerator:
     vocabs: list
     _similarity: dict = dataclasses.field(default_factory=dict, repr=False)   # (real table, n) -> its evaluator
     _privacy: dict = dataclasses.field(default_factory=dict, repr=False)      # the same for privacy()
+    _correlation: dict = dataclasses.field(default_factory=dict, repr=False)  # and for correlation()
 
     def sample(self, n: int, where=None, max_passes: int = 64) -> np.ndarray:
         """[n, n_columns] decoded values (label codes for categoricals), float64.  A GPU table comes
@@ -110,11 +111,40 @@ class LoadedGenerator:
                             max_passes: int = 64):
         """:meth:`write_csv` with :meth:`score` (score_real) and / or :meth:`privacy` (privacy_real) of the rows the
         CSV holds, both taken on the device before the copy.  Returns ((Avg_JSD, Avg_WD) | None, privacy dict | None)."""
+        return self.write_csv_all(path, n, score_real=score_real, privacy_real=privacy_real, threads=threads,
+                                  where=where, max_passes=max_passes)[:2]
+
+    def write_csv_all(self, path: str, n: int, score_real=None, privacy_real=None, corr_real=None, threads: int = 0,
+                      where=None, max_passes: int = 64):
+        """:meth:`write_csv` with whichever of :meth:`score` (score_real), :meth:`privacy` (privacy_real) and
+        :meth:`correlation` (corr_real) are asked for, all of the rows the CSV holds and all taken on the device
+        before the copy.  Returns ((Avg_JSD, Avg_WD) | None, privacy dict | None, correlation dict | None)."""
         vals = self.device_table(n, where=where, max_passes=max_passes)
         sim = self._evaluator(score_real, n).score(vals) if score_real is not None else None
         priv = self._privacy_evaluator(privacy_real, n).score(vals) if privacy_real is not None else None
+        corr = self._correlation_evaluator(corr_real, n).score(vals) if corr_real is not None else None
         self._write_values(path, self._to_host(vals), threads)
-        return (sim.floats() if sim is not None else None), (priv.floats() if priv is not None else None)
+        return tuple(s.floats() if s is not None else None for s in (sim, priv, corr))
+
+    def correlation(self, real, n: int = 40000, where=None, max_passes: int = 64) -> dict:
+        """Diff. Corr. of n generated rows against ``real`` (a DataFrame or a CSV path): generated and scored on the
+        engine's device (eval/correlation.py), only the four numbers come back: ``corr_diff`` (the Frobenius
+        distance between the two tables' association matrices), ``corr_mean_abs`` / ``corr_max_abs`` over the column
+        pairs, and the real table's own even / odd row ``corr_diff_rr`` as the baseline.  The evaluator is kept per
+        real table and n."""
+        return self._correlation_evaluator(real, n).score(
+            self.device_table(n, where=where, max_passes=max_passes)).floats()
+
+    def _correlation_evaluator(self, real, n: int):
+        import pandas as pd
+        from ..eval.correlation import DeviceCorrelation
+        key = (real if isinstance(real, str) else id(real), int(n))
+        if key not in self._correlation:
+            frame = pd.read_csv(real) if isinstance(real, str) else real
+            self._correlation.clear()
+            self._correlation[key] = (frame, DeviceCorrelation(frame, self.meta, self.vocabs, self.engine.device,
+                                                               ops=self.engine.ops, max_rows=int(n)))
+        return self._correlation[key][1]
 
     def privacy(self, real, n: int = 40000, where=None, max_passes: int = 64) -> dict:
         """DCR / NNDR of n generated rows against ``real`` (a DataFrame or a CSV path): generated and scored on the

@@ -658,3 +658,39 @@ class HipOps:
         self.L.nn_stats(d1, d2, int(n), keys, part)
         self.L.sim_sort(keys, tmp, int(n))
         self.L.nn_percentiles(keys, int(n), part, out)
+
+    # ------------------------------------------------------------------ correlation evaluator (kernels/correlation.hip)
+    CORR_CONT, CORR_CAT = 0, 1
+    CORR_CHUNK = 1024        # kernels/launch.h: rows per chunk of corr_moments (a row group is a whole number of them)
+    CORR_LDS_BINS = 16384    # the largest contingency table counted in LDS; a larger one counts in global memory
+
+    @staticmethod
+    def corr_part(n_max: int, W: int, n_cont: int) -> int:
+        """float64 scratch elements corr_pack / corr_moments need for any table of up to n_max rows"""
+        return int(native.require().corr_part(int(n_max), int(W), int(n_cont)))
+
+    @staticmethod
+    def corr_groups(n: int, W: int, n_cont: int) -> int:
+        """row groups (partials per entry of G) corr_moments uses for n rows"""
+        return int(native.require().corr_groups(int(n), int(W), int(n_cont)))
+
+    def corr_pack(self, values, kind, slot, card, cont, cat_t, mean, part):
+        """Same contract as TorchOps.corr_pack; part: float64 [>= corr_part(n, W, n_cont)]."""
+        self.L.corr_pack(values, kind, slot, card, cont, cat_t, mean, part)
+
+    def corr_moments(self, cont, cat_t, n, mean, card, offs, G, part):
+        """Same contract as TorchOps.corr_moments."""
+        self.L.corr_moments(cont, cat_t, int(n), mean, card, offs, G, part)
+
+    def corr_counts(self, cat_t, n, pairs, poff, counts, lds_bins=None):
+        """Same contract as TorchOps.corr_counts; lds_bins: the largest table counted in LDS (<= CORR_LDS_BINS)."""
+        self.L.corr_counts(cat_t, int(n), pairs, poff, counts,
+                           self.CORR_LDS_BINS if lds_bins is None else int(lds_bins))
+
+    def corr_matrix(self, G, counts, poff, kind, slot, card, offs, n, A):
+        """Same contract as TorchOps.corr_matrix."""
+        self.L.corr_matrix(G, counts, poff, kind, slot, card, offs, int(n), A)
+
+    def corr_diff(self, A, B, out):
+        """Same contract as TorchOps.corr_diff."""
+        self.L.corr_diff(A, B, out)

@@ -588,3 +588,151 @@ class TorchOps:
                 out[row] = v - (v - u) * (1.0 - t) if t >= 0.5 else u + (v - u) * t
         out[2] = keys[0, 0]
         out[3] = (a == 0).sum().to(torch.float64) / n
+
+    # ------------------------------------------------------------------ correlation evaluator
+    CORR_CONT, CORR_CAT = 0, 1
+    CORR_CHUNK, CORR_LDS_BINS = 1024, 16384     # the HIP kernels' row chunk and LDS table limit; shared attributes only
+    CORR_CELLS = 1 << 24                         # table cells corr_counts holds at a time
+
+    @staticmethod
+    def corr_part(n_max: int, W: int, n_cont: int) -> int:
+        return 1
+
+    @staticmethod
+    def corr_groups(n: int, W: int, n_cont: int) -> int:
+        return 1
+
+    def corr_pack(self, values, kind, slot, card, cont, cat_t, mean, part=None):
+        """One pass over a decoded table values [n, n_cols] float64 (eval/correlation.py DeviceCorrelation).
+
+        kind / slot int32 [n_cols]: a continuous column (CORR_CONT) becomes column slot of cont [>= n, n_cont]
+        unchanged and mean[slot] = its sum / n; a categorical column (CORR_CAT) becomes row slot of cat_t
+        [n_cat, >= n] int32: its code truncated to an integer when it lies in [0, card[slot]), else (NaN included)
+        the overflow bin card[slot]."""
+        n = values.shape[0]
+        dev = values.device
+        kl, sl = kind.tolist(), slot.tolist()
+        cc = [c for c, k in enumerate(kl) if k == self.CORR_CONT]
+        kc = [c for c, k in enumerate(kl) if k == self.CORR_CAT]
+        if cc:
+            cs = torch.tensor([sl[c] for c in cc], dtype=torch.long, device=dev)
+            cont[:n, cs] = values[:, torch.tensor(cc, dtype=torch.long, device=dev)]
+            mean.copy_(cont[:n].sum(dim=0) / n)
+        if kc:
+            ks = torch.tensor([sl[c] for c in kc], dtype=torch.long, device=dev)
+            v = values[:, torch.tensor(kc, dtype=torch.long, device=dev)]
+            K = card[ks].to(torch.float64)[None, :]
+            ok = (v >= 0) & (v < K)
+            cat_t[ks, :n] = torch.where(ok, v, K.expand_as(v)).t().to(cat_t.dtype)
+
+    def corr_moments(self, cont, cat_t, n, mean, card, offs, G, part=None):
+        """G [W, n_cont] = F^T Xc in float64 with Xc = cont[:n] - mean and F = [Xc | one-hot(codes)]: rows
+        [0, n_cont) hold the centred cross sums, row n_cont + offs[c] + k the sum of Xc over the rows whose code in
+        categorical column c is k (k <= card[c]; codes are clamped into that range).  The one-hot is never built: the
+        rows of Xc are added into the bins their codes select, one column at a time.  On a GPU index_add_ is a
+        floating-point atomic scatter, so two runs may differ in the last bits there: the bit-identical guarantee of
+        the contract holds for HipOps, and for these ops on the CPU only."""
+        nc = cont.shape[1]
+        if nc == 0:
+            return
+        xc = cont[:n] - mean[None, :]
+        G[:nc] = xc.t() @ xc
+        for c, (K, o) in enumerate(zip(card.tolist(), offs.tolist())):
+            block = torch.zeros(K + 1, nc, dtype=G.dtype, device=G.device)
+            block.index_add_(0, cat_t[c, :n].long().clamp(0, K), xc)
+            G[nc + o:nc + o + K + 1] = block
+
+    def corr_counts(self, cat_t, n, pairs, poff, counts, lds_bins=None):
+        """counts (int32, flat) = the contingency tables the pair list asks for.  pairs int32 [P, 4] = (column a,
+        column b or -1 for the margin of a, bins of a, bins of b); table p starts at poff[p] (int64 [P + 1]) and is
+        row-major [bins of a][bins of b].  Codes are clamped into their bins.  Works on blocks of pairs that share
+        column a, so only CORR_CELLS row-table cells exist at a time."""
+        counts.zero_()
+        pl, po = pairs.tolist(), poff.tolist()
+        dev = cat_t.device
+        block = max(1, self.CORR_CELLS // max(n, 1))
+        i, P = 0, len(pl)
+        while i < P:
+            a, ka = pl[i][0], pl[i][2]
+            j = i
+            while j < P and j - i < block and pl[j][0] == a and pl[j][2] == ka:
+                j += 1
+            ca = cat_t[a, :n].long().clamp(0, ka - 1)
+            b = torch.tensor([q[1] for q in pl[i:j]], dtype=torch.long, device=dev)
+            kb = torch.tensor([q[3] for q in pl[i:j]], dtype=torch.long, device=dev)
+            base = torch.tensor([o - po[i] for o in po[i:j]], dtype=torch.long, device=dev)
+            cb = cat_t[b.clamp_min(0), :n].long().clamp_min(0)
+            cb = torch.minimum(cb, (kb - 1)[:, None])
+            cb = torch.where((b >= 0)[:, None], cb, torch.zeros_like(cb))
+            flat = base[:, None] + ca[None, :] * kb[:, None] + cb
+            counts[po[i]:po[j]] += torch.bincount(flat.flatten(), minlength=po[j] - po[i]).to(counts.dtype)
+            i = j
+
+    def corr_matrix(self, G, counts, poff, kind, slot, card, offs, n, A):
+        """A [C, C] float64, the association matrix of the contract (eval/correlation.py): Pearson r from G's top
+        block, the correlation ratio from the per-category sums and the margins, Theil's U(i|j) from the tables.
+        The tables of poff: the n_cat margins first, then the pairs a < b in row-major order."""
+        dev = A.device
+        kl, sl = kind.tolist(), slot.tolist()
+        cl, ol, po = card.tolist(), offs.tolist(), poff.tolist()
+        n_cat = len(cl)
+        nc = A.shape[0] - n_cat
+        col_cont = [0] * nc
+        col_cat = [0] * n_cat
+        for c, (k, s) in enumerate(zip(kl, sl)):
+            (col_cat if k == self.CORR_CAT else col_cont)[s] = c
+        A.zero_()
+        A.fill_diagonal_(1.0)
+        nf = float(n)
+        if nc:
+            ci = torch.tensor(col_cont, dtype=torch.long, device=dev)
+            d = torch.diagonal(G[:nc]).clone()
+            den = torch.sqrt(d[:, None] * d[None, :])
+            ok = (d[:, None] > 0) & (d[None, :] > 0)
+            r = torch.where(ok, G[:nc] / torch.where(ok, den, torch.ones_like(den)), torch.zeros_like(den))
+            r = r.clamp(-1.0, 1.0)
+            r.fill_diagonal_(1.0)
+            A[ci[:, None], ci[None, :]] = r
+        margins, entropy = [], []
+        for c in range(n_cat):
+            m = counts[po[c]:po[c] + cl[c] + 1].to(torch.float64)
+            p = m / nf
+            h = -(torch.where(m > 0, p * torch.log(torch.where(m > 0, p, torch.ones_like(p))), torch.zeros_like(p))).sum()
+            margins.append(m)
+            entropy.append(h)
+            if nc:
+                S = G[nc + ol[c]:nc + ol[c] + cl[c] + 1]
+                mm = torch.where(m > 0, m, torch.ones_like(m))[:, None]
+                val = torch.where((m > 0)[:, None], S * S / mm, torch.zeros_like(S)).sum(dim=0)
+                eta = torch.where(d > 0, torch.sqrt(val / torch.where(d > 0, d, torch.ones_like(d))),
+                                  torch.zeros_like(d)).clamp(0.0, 1.0)
+                A[col_cat[c], ci] = eta
+                A[ci, col_cat[c]] = eta
+        one = torch.ones((), dtype=torch.float64, device=dev)
+        p = n_cat
+        for a in range(n_cat):
+            for b in range(a + 1, n_cat):
+                ka, kb = cl[a] + 1, cl[b] + 1
+                T = counts[po[p]:po[p] + ka * kb].view(ka, kb).to(torch.float64)
+                p += 1
+                pos = T > 0
+                Ts = torch.where(pos, T, torch.ones_like(T))
+                zero = torch.zeros_like(T)
+                h_ab = torch.where(pos, (T / nf) * torch.log(margins[b][None, :] / Ts), zero).sum()   # H(a | b)
+                h_ba = torch.where(pos, (T / nf) * torch.log(margins[a][:, None] / Ts), zero).sum()   # H(b | a)
+                ha, hb = entropy[a], entropy[b]
+                A[col_cat[a], col_cat[b]] = torch.where(ha > 0, ((ha - h_ab) / torch.where(ha > 0, ha, one))
+                                                        .clamp(0.0, 1.0), one)
+                A[col_cat[b], col_cat[a]] = torch.where(hb > 0, ((hb - h_ba) / torch.where(hb > 0, hb, one))
+                                                        .clamp(0.0, 1.0), one)
+
+    def corr_diff(self, A, B, out):
+        """out[0] = ||A - B||_F; out[1] = the mean and out[2] = the maximum of |A - B| over the off-diagonal entries
+        (both 0 for a 1 x 1 matrix)."""
+        C = A.shape[0]
+        d = (A - B).abs()
+        out[0] = torch.sqrt((d * d).sum())
+        off = d.clone()
+        off.fill_diagonal_(0.0)
+        out[1] = off.sum() / (C * (C - 1)) if C > 1 else 0.0
+        out[2] = off.max() if C > 1 else 0.0
