@@ -1432,6 +1432,141 @@ int64_t corr_lds_bins() { return fedtgan::CORR_LDS_BINS; }
 int64_t corr_part(int64_t n_max, int64_t W, int64_t n_cont) { return fedtgan::corr_part_doubles(n_max, W, n_cont); }
 int64_t corr_groups(int64_t n, int64_t W, int64_t n_cont) { return fedtgan::corr_groups(n, W, n_cont).groups; }
 
+// ----------------------------------------------------------------------------- ML-utility evaluator
+namespace {
+// the packed table of the util_* ops: cont [>= n, n_cont], cat_t [n_cat, >= n], y / s [>= n], counts [K], info [4]
+fedtgan::UtilTable util_table(const char* what, const Tensor& cont, const Tensor& cat_t, const Tensor& y,
+                              const Tensor& s, const Tensor& counts, const Tensor& info, const Tensor& card,
+                              const Tensor& offs, int64_t n, int64_t D) {
+  TORCH_CHECK(n >= 1 && n < (int64_t)INT32_MAX, what, ": n");
+  TORCH_CHECK(sim_f64(cont) && cont.dim() == 2 && cont.size(0) >= n && sim_i32(cat_t) && cat_t.dim() == 2 &&
+                  cat_t.size(1) >= n, what, ": cont float64 [>= n, n_cont], cat_t int32 [n_cat, >= n]");
+  TORCH_CHECK(sim_i32(y) && y.numel() >= n && sim_f64(s) && s.numel() >= n, what, ": y int32 [>= n], s float64 [>= n]");
+  const int64_t n_cat = cat_t.size(0), n_cont = cont.size(1), K = counts.numel();
+  TORCH_CHECK(sim_i32(counts) && K >= 1 && K <= fedtgan::UTIL_MAX_CLASSES && sim_f64(info) && info.numel() >= 4, what,
+              ": counts int32 [K <= UTIL_MAX_CLASSES], info float64 [4]");
+  TORCH_CHECK(sim_i32(card) && card.numel() == n_cat && sim_i32(offs) && offs.numel() == n_cat + 1, what,
+              ": card int32 [n_cat], offs int32 [n_cat + 1]");
+  TORCH_CHECK(D >= n_cont + 2 * n_cat + 1 && D <= fedtgan::UTIL_MAX_FEATURES, what,
+              ": D must cover the features and stay within UTIL_MAX_FEATURES");
+  fedtgan::UtilTable t{};
+  t.cont = n_cont ? cont.data_ptr<double>() : nullptr;
+  t.cat_t = n_cat ? cat_t.data_ptr<int>() : nullptr;
+  t.y = y.data_ptr<int>();
+  t.s = s.data_ptr<double>();
+  t.counts = counts.data_ptr<int>();
+  t.info = info.data_ptr<double>();
+  t.ldk = cat_t.size(1);
+  t.n = (int)n;
+  t.n_cont = (int)n_cont;
+  t.n_cat = (int)n_cat;
+  t.D = (int)D;
+  t.K = (int)K;
+  t.card = n_cat ? card.data_ptr<int>() : nullptr;
+  t.offs = offs.data_ptr<int>();
+  return t;
+}
+
+void util_check_point(const char* what, const Tensor& P, int64_t D, int64_t K) {
+  TORCH_CHECK(sim_f64(P) && P.dim() == 2 && P.size(0) == D && P.size(1) == K, what, ": float64 [D, K] expected");
+}
+}  // namespace
+
+void util_pack(const Tensor& values, const Tensor& kind, const Tensor& slot, const Tensor& card, const Tensor& offs,
+               const Tensor& mean, const Tensor& sd, int64_t D, const Tensor& cont, const Tensor& cat_t,
+               const Tensor& y, const Tensor& s, const Tensor& counts, const Tensor& info) {
+  TORCH_CHECK(sim_f64(values) && values.dim() == 2 && values.size(0) >= 1 && values.size(1) >= 1,
+              "util_pack: values must be contiguous float64 [rows >= 1, n_cols]");
+  TORCH_CHECK(values.numel() < (int64_t)INT32_MAX, "util_pack: a table holds fewer than 2^31 values");
+  TORCH_CHECK(sim_i32(kind) && sim_i32(slot) && kind.numel() == values.size(1) && slot.numel() == values.size(1),
+              "util_pack: int32 kind / slot, one entry per column");
+  fedtgan::UtilPackArgs a{};
+  a.t = util_table("util_pack", cont, cat_t, y, s, counts, info, card, offs, values.size(0), D);
+  TORCH_CHECK(cont.size(1) + cat_t.size(0) + 1 == values.size(1), "util_pack: n_cont + n_cat + 1 must be n_cols");
+  TORCH_CHECK(sim_f64(mean) && sim_f64(sd) && mean.numel() == cont.size(1) && sd.numel() == cont.size(1),
+              "util_pack: mean / sd float64 [n_cont]");
+  a.values = values.data_ptr<double>();
+  a.n_cols = (int)values.size(1);
+  a.kind = kind.data_ptr<int>();
+  a.slot = slot.data_ptr<int>();
+  a.mean = a.t.n_cont ? mean.data_ptr<double>() : nullptr;
+  a.sd = a.t.n_cont ? sd.data_ptr<double>() : nullptr;
+  fedtgan::launch_util_pack(a, cur_stream());
+}
+
+void util_gram(const Tensor& cont, const Tensor& cat_t, const Tensor& y, const Tensor& s, const Tensor& counts,
+               const Tensor& info, const Tensor& card, const Tensor& offs, int64_t n, const Tensor& M,
+               const Tensor& part) {
+  TORCH_CHECK(sim_f64(M) && M.dim() == 2 && M.size(0) == M.size(1) && M.size(0) >= 1, "util_gram: M float64 [D, D]");
+  const int64_t D = M.size(0);
+  const fedtgan::UtilTable t = util_table("util_gram", cont, cat_t, y, s, counts, info, card, offs, n, D);
+  const int64_t need = (int64_t)fedtgan::util_groups(n, D * D).groups * D * D;
+  TORCH_CHECK(sim_f64(part) && part.numel() >= need, "util_gram: part needs ", need, " float64");
+  fedtgan::launch_util_gram(t, M.data_ptr<double>(), part.data_ptr<double>(), cur_stream());
+}
+
+void util_factor(const Tensor& M, const Tensor& Lt, const Tensor& X, const Tensor& Minv) {
+  TORCH_CHECK(sim_f64(M) && M.dim() == 2 && M.size(0) == M.size(1) && M.size(0) >= 1 &&
+                  M.size(0) <= fedtgan::UTIL_MAX_FEATURES, "util_factor: M float64 [D, D], D <= UTIL_MAX_FEATURES");
+  for (const Tensor* t : {&Lt, &X, &Minv})
+    TORCH_CHECK(sim_f64(*t) && t->numel() == M.numel(), "util_factor: Lt, X, Minv float64 [D, D]");
+  fedtgan::launch_util_factor(M.data_ptr<double>(), (int)M.size(0), Lt.data_ptr<double>(), X.data_ptr<double>(),
+                              Minv.data_ptr<double>(), cur_stream());
+}
+
+void util_grad(const Tensor& cont, const Tensor& cat_t, const Tensor& y, const Tensor& s, const Tensor& counts,
+               const Tensor& info, const Tensor& card, const Tensor& offs, int64_t n, const Tensor& P, const Tensor& G,
+               const Tensor& loss, const Tensor& part, const Tensor& lossp) {
+  TORCH_CHECK(P.dim() == 2, "util_grad: P float64 [D, K]");
+  const int64_t D = P.size(0), K = counts.numel();
+  const fedtgan::UtilTable t = util_table("util_grad", cont, cat_t, y, s, counts, info, card, offs, n, D);
+  util_check_point("util_grad: P", P, D, K);
+  util_check_point("util_grad: G", G, D, K);
+  const int64_t groups = fedtgan::util_groups(n, D * K).groups;
+  TORCH_CHECK(sim_f64(part) && part.numel() >= groups * D * K && sim_f64(lossp) && lossp.numel() >= groups,
+              "util_grad: part needs ", groups * D * K, " float64, lossp ", groups);
+  TORCH_CHECK(sim_f64(loss) && loss.numel() >= 1, "util_grad: loss float64 [1]");
+  fedtgan::launch_util_grad(t, P.data_ptr<double>(), G.data_ptr<double>(), loss.data_ptr<double>(),
+                            part.data_ptr<double>(), lossp.data_ptr<double>(), cur_stream());
+}
+
+void util_step(const Tensor& cont, const Tensor& cat_t, const Tensor& y, const Tensor& s, const Tensor& counts,
+               const Tensor& info, const Tensor& card, const Tensor& offs, int64_t n, const Tensor& V, const Tensor& W,
+               const Tensor& Minv, const Tensor& G, const Tensor& loss, const Tensor& part, const Tensor& lossp,
+               double beta) {
+  util_grad(cont, cat_t, y, s, counts, info, card, offs, n, V, G, loss, part, lossp);
+  const int64_t D = V.size(0), K = V.size(1);
+  util_check_point("util_step: W", W, D, K);
+  TORCH_CHECK(sim_f64(Minv) && Minv.dim() == 2 && Minv.size(0) == D && Minv.size(1) == D,
+              "util_step: Minv float64 [D, D]");
+  fedtgan::launch_util_update(V.data_ptr<double>(), W.data_ptr<double>(), Minv.data_ptr<double>(),
+                              G.data_ptr<double>(), (int)D, (int)K, beta, cur_stream());
+}
+
+void util_predict(const Tensor& cont, const Tensor& cat_t, const Tensor& y, const Tensor& s, const Tensor& counts,
+                  const Tensor& info, const Tensor& card, const Tensor& offs, int64_t n, const Tensor& train_counts,
+                  const Tensor& W, const Tensor& conf, const Tensor& G, const Tensor& loss, const Tensor& real,
+                  const Tensor& out) {
+  TORCH_CHECK(W.dim() == 2, "util_predict: W float64 [D, K]");
+  const int64_t D = W.size(0), K = counts.numel();
+  const fedtgan::UtilTable t = util_table("util_predict", cont, cat_t, y, s, counts, info, card, offs, n, D);
+  util_check_point("util_predict: W", W, D, K);
+  util_check_point("util_predict: G", G, D, K);
+  TORCH_CHECK(sim_i32(train_counts) && train_counts.numel() == K && sim_i32(conf) && conf.numel() == K * K,
+              "util_predict: train_counts int32 [K], conf int32 [K, K]");
+  TORCH_CHECK(sim_f64(loss) && loss.numel() >= 1 && sim_f64(real) && real.numel() >= 2 && sim_f64(out) &&
+                  out.numel() >= 8, "util_predict: loss [1], real [2], out [8] float64");
+  fedtgan::launch_util_predict(t, train_counts.data_ptr<int>(), W.data_ptr<double>(), conf.data_ptr<int>(),
+                               G.data_ptr<double>(), loss.data_ptr<double>(), real.data_ptr<double>(),
+                               out.data_ptr<double>(), cur_stream());
+}
+
+int64_t util_max_features() { return fedtgan::UTIL_MAX_FEATURES; }
+int64_t util_max_classes() { return fedtgan::UTIL_MAX_CLASSES; }
+int64_t util_chunk() { return fedtgan::UTIL_CHUNK; }
+int64_t util_part(int64_t n_max, int64_t D, int64_t K) { return fedtgan::util_part_doubles(n_max, D, K); }
+int64_t util_groups(int64_t n, int64_t cells) { return fedtgan::util_groups(n, cells).groups; }
+
 // ----------------------------------------------------------------------------- native RCCL plane (csrc/comm)
 void rccl_load_op(const std::string& path) { fedtgan::comm::rccl_load(path); }
 
@@ -1930,6 +2065,23 @@ TORCH_LIBRARY(fedtgan, m) {
   m.def("corr_part(int n_max, int W, int n_cont) -> int", &corr_part);
   m.def("corr_groups(int n, int W, int n_cont) -> int", &corr_groups);
   m.def(
+      "util_pack(Tensor values, Tensor kind, Tensor slot, Tensor card, Tensor offs, Tensor mean, Tensor sd, int D, "
+      "Tensor(a!) cont, Tensor(b!) cat_t, Tensor(c!) y, Tensor(d!) s, Tensor(e!) counts, Tensor(f!) info) -> ()");
+  m.def("util_gram(Tensor cont, Tensor cat_t, Tensor y, Tensor s, Tensor counts, Tensor info, Tensor card, Tensor offs, int n, Tensor(a!) M, Tensor(b!) part) -> ()");
+  m.def("util_factor(Tensor M, Tensor(a!) Lt, Tensor(b!) X, Tensor(c!) Minv) -> ()");
+  m.def("util_grad(Tensor cont, Tensor cat_t, Tensor y, Tensor s, Tensor counts, Tensor info, Tensor card, Tensor offs, int n, Tensor P, Tensor(a!) G, Tensor(b!) loss, Tensor(c!) part, Tensor(d!) lossp) -> ()");
+  m.def(
+      "util_step(Tensor cont, Tensor cat_t, Tensor y, Tensor s, Tensor counts, Tensor info, Tensor card, Tensor offs, int n, Tensor(a!) V, Tensor(b!) W, Tensor Minv, Tensor(c!) G, Tensor(d!) loss, Tensor(e!) part, "
+      "Tensor(f!) lossp, float beta) -> ()");
+  m.def(
+      "util_predict(Tensor cont, Tensor cat_t, Tensor y, Tensor s, Tensor counts, Tensor info, Tensor card, Tensor offs, int n, Tensor train_counts, Tensor W, Tensor(a!) conf, Tensor G, Tensor loss, Tensor real, "
+      "Tensor(b!) out) -> ()");
+  m.def("util_max_features() -> int", &util_max_features);
+  m.def("util_max_classes() -> int", &util_max_classes);
+  m.def("util_chunk() -> int", &util_chunk);
+  m.def("util_part(int n_max, int D, int K) -> int", &util_part);
+  m.def("util_groups(int n, int cells) -> int", &util_groups);
+  m.def(
       "vgm_estep(Tensor x, Tensor n_rows, Tensor consts, Tensor means, Tensor prec, Tensor(a!) partial, "
       "int rows_per_block) -> ()");
   m.def("kmeans_step(Tensor x, Tensor n_rows, Tensor centers, Tensor(a!) partial, int rows_per_block) -> ()");
@@ -1998,6 +2150,12 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("corr_counts", &corr_counts);
   m.impl("corr_matrix", &corr_matrix);
   m.impl("corr_diff", &corr_diff);
+  m.impl("util_pack", &util_pack);
+  m.impl("util_gram", &util_gram);
+  m.impl("util_factor", &util_factor);
+  m.impl("util_grad", &util_grad);
+  m.impl("util_step", &util_step);
+  m.impl("util_predict", &util_predict);
   m.impl("vgm_encode", &vgm_encode);
   m.impl("vgm_estep", &vgm_estep);
   m.impl("kmeans_step", &kmeans_step);

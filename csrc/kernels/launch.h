@@ -617,6 +617,60 @@ void launch_corr_matrix(const CorrMatrixArgs& a, hipStream_t stream);
 // out[0] = ||A - B||_F, out[1] = mean |A - B| over the off-diagonal entries (0 for C == 1), out[2] = their maximum
 void launch_corr_diff(const double* A, const double* B, int C, double* out, hipStream_t stream);
 
+// ML-utility evaluator (kernels/utility.hip): a class-balanced, L2-regularised multinomial logistic regression fitted
+// on a decoded table by a fixed number of bound-preconditioned accelerated gradient steps, and its confusion matrix on
+// held-out rows (eval/utility_device.py has the definition).  All fp64; every sum has an order fixed by the shapes
+// alone, counting is in integers; no floating-point atomics, no allocation, no host round trip.
+// The limits: a lane of the one-workgroup factorisation owns one column of the [D, D] matrix (1024 threads), and a
+// 64-row block of logits [64, K] lives in 33 KiB of LDS, so four workgroups share a CU's 160 KiB.
+constexpr int UTIL_MAX_FEATURES = 1024;     // D: continuous columns + one-hot bins (with overflow bins) + intercept
+constexpr int UTIL_MAX_CLASSES = 64;        // K: categories of the target column
+constexpr int UTIL_ROWS = 64;               // rows of a block of logits / residuals in LDS
+constexpr int UTIL_CHUNK = 128;             // rows per chunk; a row group is a whole number of consecutive chunks
+constexpr int UTIL_SLAB = 256;              // features (rows of F^T R) per workgroup of the gradient
+constexpr int64_t UTIL_PART_TARGET = 8ll << 20;   // fp64 partials (64 MiB) the row groups of one product may fill
+enum UtilKind : int { UTIL_CONT = 0, UTIL_CAT = 1, UTIL_TARGET = 2 };
+// the row split of n rows whose partials hold `cells` doubles each (a function of the shape alone)
+CorrGroups util_groups(int64_t n, int64_t cells);
+int64_t util_part_doubles(int64_t n_max, int64_t D, int64_t K);   // what gram and step need for any n <= n_max
+// a packed table: standardised continuous features, clamped feature codes, target codes and sample weights
+struct UtilTable {
+  double* cont;           // [>= n, n_cont] (v - mean) / sd, row-major
+  int* cat_t;             // [n_cat, ldk] codes of the categorical features, overflow bin card[c] included
+  int* y;                 // [>= n] target code, K where the value is no code of [0, K)
+  double* s;              // [>= n] sample weight, 0 where y == K
+  int* counts;            // [K] rows per class
+  double* info;           // [4]: n_valid, classes present, S = sum of s, unused
+  int64_t ldk;
+  int n, n_cont, n_cat, D, K;
+  const int* card;        // [n_cat]
+  const int* offs;        // [n_cat + 1] first one-hot feature of a column, less n_cont; offs[n_cat] = D - 1 - n_cont
+};
+struct UtilPackArgs {
+  const double* values;   // [rows, n_cols] decoded table, row-major
+  int n_cols;
+  const int* kind;        // [n_cols] UtilKind
+  const int* slot;        // [n_cols] column of cont / row of cat_t
+  const double* mean;     // [n_cont]
+  const double* sd;       // [n_cont] (> 0)
+  UtilTable t;
+};
+void launch_util_pack(const UtilPackArgs& a, hipStream_t stream);
+// M [D, D] = (F^T diag(s) F / 2 + diag(reg)) / S, reg = 1 but for the intercept's 0; part: [groups, D, D]
+void launch_util_gram(const UtilTable& t, double* M, double* part, hipStream_t stream);
+// Minv = (M + 1e-10 trace(M) / D I)^-1 through the Cholesky factor; Lt, X: [D, D] scratch
+void launch_util_factor(const double* M, int D, double* Lt, double* X, double* Minv, hipStream_t stream);
+// G [D, K] = grad f(P), loss[0] = f(P); part: [groups, D, K], lossp: [groups]
+void launch_util_grad(const UtilTable& t, const double* P, double* G, double* loss, double* part, double* lossp,
+                      hipStream_t stream);
+// W' = V - Minv G; V' = W' + beta (W' - W)
+void launch_util_update(double* V, double* W, const double* Minv, const double* G, int D, int K, double beta,
+                        hipStream_t stream);
+// conf [K, K] int32 of the rows of t under weights W (classes with train_counts == 0 are never predicted);
+// out[0..7] = f1, acc, real[0], real[1], real[0] - f1, real[1] - acc, loss[0], max |G|
+void launch_util_predict(const UtilTable& t, const int* train_counts, const double* W, int* conf, const double* G,
+                         const double* loss, const double* real, double* out, hipStream_t stream);
+
 struct GenWeightJob {
   const float* w;   // fp32 weight, element (n, k) at w[n * ldw + k * skw] (skw = 1: [N, K] rows; ldw = 1: input-major storage)
   int N, ldw, skw, kd, C;

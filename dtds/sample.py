@@ -37,7 +37,16 @@ def main(argv=None):
                    help="also print one JSON line with Diff. Corr. of the generated rows against this table (the "
                         "distance between the two tables' association matrices, its mean and maximum per column "
                         "pair, and the real table's own even / odd row baseline)")
+    p.add_argument("-utility_against", default=None, metavar="REAL.csv",
+                   help="also print one JSON line with the ML utility of the generated rows: weighted F1 and accuracy "
+                        "on held-out real rows of a logistic regression fitted on them on the device, the same for "
+                        "the real training rows, and the gaps (real - generated)")
+    p.add_argument("-utility_test", default=None, metavar="TEST.csv",
+                   help="the held-out real rows of -utility_against (default: its rows with index %% 5 == 4)")
+    p.add_argument("-utility_iters", type=int, default=200, help="solver iterations of -utility_against")
     args = p.parse_args(argv)
+    if (args.utility_test or args.utility_iters != 200) and not args.utility_against:
+        p.error("-utility_test / -utility_iters need -utility_against")
     import torch
     from fed_tgan_amd.models.conditional import parse_where
     from fed_tgan_amd.models.generator_io import load_generator
@@ -46,11 +55,12 @@ def main(argv=None):
     gen = load_generator(args.model, dev, backend=args.backend, seed=args.seed)
     out = args.out or f"{gen.name}_synthetic.csv"
     t0 = time.time()
-    scores = privacy = corr = None
-    if args.score_against or args.privacy_against or args.corr_against:
-        scores, privacy, corr = gen.write_csv_all(out, args.n, score_real=args.score_against,
-                                                  privacy_real=args.privacy_against, corr_real=args.corr_against,
-                                                  where=where or None, max_passes=args.max_passes)
+    scores = privacy = corr = utility = None
+    if args.score_against or args.privacy_against or args.corr_against or args.utility_against:
+        scores, privacy, corr, utility = gen.write_csv_all(
+            out, args.n, score_real=args.score_against, privacy_real=args.privacy_against,
+            corr_real=args.corr_against, where=where or None, max_passes=args.max_passes,
+            utility_real=args.utility_against, utility_test=args.utility_test, utility_iters=args.utility_iters)
     else:
         gen.write_csv(out, args.n, where=where or None, max_passes=args.max_passes)
     cond = ""
@@ -64,6 +74,8 @@ def main(argv=None):
         print(json.dumps(privacy), flush=True)
     if corr is not None:
         print(json.dumps(corr), flush=True)
+    if utility is not None:
+        print(json.dumps(utility), flush=True)
     return out
 
 

@@ -1,2 +1,3 @@
 from .correlation import CorrelationScores, DeviceCorrelation  # noqa: F401
 from .privacy import DevicePrivacy, PrivacyScores  # noqa: F401
+from .utility_device import DeviceUtility, UtilityScores  # noqa: F401

@@ -1,0 +1,274 @@
+"""On-device ML-utility evaluator: train on the generated table, test on real rows (TSTR), and report the gap to the
+same classifier trained on the real training rows.
+
+Avg_JSD / Avg_WD, DCR / NNDR and Diff. Corr. compare the tables; this evaluator asks whether a model fitted on the
+generated rows classifies held-out real rows.  The classifier is a class-balanced, L2-regularised multinomial logistic
+regression only; the reference's decision tree, random forest and MLP stay with ``eval/utility.py`` (sklearn on a CSV).
+Rows live in the space of the decoded table (``generate_decoded``'s ``[n, n_cols]`` float64: label codes in the
+categorical columns, log1p values in the ``non_negative_cols``); the real tables are brought there with
+:func:`fed_tgan_amd.eval.privacy.code_real_table`.
+
+**Target.**  ``meta["target"]`` (or ``target=``), a categorical column with ``K`` categories (``K`` and every
+``K_c`` below by the rule of :class:`DeviceCorrelation`: ``max(len(vocab), 1 + largest real code)``).  A training
+row whose target is NaN or no code of ``[0, K)`` gets weight 0; such a test row is skipped.
+
+**Features.**  Every other column.  A continuous column is ``(v - mean) / sd`` with the mean and the population sd
+of the pooled real table (train and test), an sd of 0 taken as 1.  A categorical column with ``K_c`` categories is a
+one-hot block of ``K_c + 1`` columns, the last for values that are no code.  A constant 1 comes last.  ``D = n_cont +
+sum(K_c + 1) + 1``; the weights ``W`` are ``[D, K]`` float64 and start at 0.  The one-hot blocks never exist in memory.
+
+**Sample weights.**  ``s_i = n_valid / (K_present count[y_i])``; classes absent from the training table have
+probability 0, keep a zero weight column and are never predicted (with no class present, class 0 is).  ``S`` is the
+sum of ``s`` (taken as 1 when no row is valid).
+
+**Objective.**  ``f(W) = (sum_i s_i CE(softmax(F_i W), y_i) + |W without the intercept row|^2 / 2) / S``, the
+objective of sklearn's ``LogisticRegression(C=1, class_weight="balanced")``.
+
+**Solver.**  ``M = (F^T diag(s) F / 2 + diag(reg)) / S`` with ``reg`` 1 but 0 for the intercept, plus ``1e-10
+trace(M) / D`` on the diagonal: Boehning's bound of the Hessian.  ``M^-1`` comes once per fit from the Cholesky
+factor.  With ``V_0 = W_0 = 0`` and ``t_0 = 1``, ``iters`` times: ``W_{k+1} = V_k - M^-1 grad f(V_k)``, ``t_{k+1} = (1
++ sqrt(1 + 4 t_k^2)) / 2``, ``V_{k+1} = W_{k+1} + (t_k - 1) / t_{k+1} (W_{k+1} - W_k)``.  The softmax subtracts the
+row maximum over the present classes.
+
+**Scores** (``KEYS``).  The prediction is the largest logit over the present classes, the lowest class on a tie; the
+confusion matrix is int32 ``[K, K]`` over the test rows; ``acc`` the accuracy and ``f1`` the support-weighted mean of
+the per-class F1 (0 for a class with ``2 tp + fp + fn == 0``).  ``*_real`` come from the same fit on the real training
+rows, done once at construction; a gap is real - fake; ``loss_fake = f(W_iters)`` and ``grad_fake = max |grad
+f(W_iters)|`` say how far the fit got.
+
+``score(values)`` is a fixed single-stream launch sequence (``ops.util_pack`` -> ``util_gram`` -> ``util_factor`` ->
+``iters`` x ``util_step`` -> ``util_grad`` -> ``util_predict``) over buffers allocated at construction, without
+allocation or host round trip, so it can be captured in a hipGraph (``graph=True``).  The ops come from
+:class:`fed_tgan_amd.ops.hip.HipOps` (kernels/utility.hip) on a GPU and from :class:`fed_tgan_amd.ops.ref.TorchOps`
+elsewhere; the second is the first's oracle.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import pandas as pd
+import torch
+
+from ..data.constants import CATEGORICAL
+from ..data.decode import meta_column_names
+from .device import GraphedPass
+from .privacy import code_real_table
+
+UTIL_CONT, UTIL_CAT, UTIL_TARGET = 0, 1, 2
+KEYS = ("f1_fake", "acc_fake", "f1_real", "acc_real", "f1_gap", "acc_gap", "loss_fake", "grad_fake")
+
+
+def momentum_table(iters: int) -> List[float]:
+    """beta_k = (t_k - 1) / t_{k+1} for k = 0 .. iters - 1, with t_0 = 1"""
+    out, t = [], 1.0
+    for _ in range(int(iters)):
+        t1 = (1.0 + math.sqrt(1.0 + 4.0 * t * t)) / 2.0
+        out.append((t - 1.0) / t1)
+        t = t1
+    return out
+
+
+class UtilityTable:
+    """The packed form of a table of up to ``rows`` rows (``ops.util_pack`` fills it)."""
+
+    def __init__(self, rows: int, n_cont: int, card: torch.Tensor, offs: torch.Tensor, D: int, K: int, device):
+        f64 = dict(dtype=torch.float64, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.cont = torch.zeros(rows, n_cont, **f64)
+        self.cat_t = torch.zeros(int(card.numel()), rows, **i32)
+        self.y = torch.zeros(rows, **i32)
+        self.s = torch.zeros(rows, **f64)
+        self.counts = torch.zeros(K, **i32)
+        self.info = torch.zeros(4, **f64)
+        self.card, self.offs, self.D, self.K = card, offs, int(D), int(K)
+
+
+class UtilityScores:
+    """Scores of one table: ``buf`` = the eight numbers of ``KEYS`` on the device.  Nothing here synchronises except
+    :meth:`floats`."""
+
+    def __init__(self, buf: torch.Tensor, conf: torch.Tensor, W: torch.Tensor):
+        self.buf = buf
+        self._conf = conf
+        self._W = W
+
+    def floats(self) -> Dict[str, float]:
+        return {k: float(v) for k, v in zip(KEYS, self.buf.cpu().tolist())}
+
+    def confusion(self) -> torch.Tensor:
+        """int32 [K, K] on the device: test rows by (real class, predicted class)"""
+        return self._conf
+
+    def weights(self) -> torch.Tensor:
+        """W [D, K] float64 on the device, the fit on the generated table"""
+        return self._W
+
+
+class DeviceUtility(GraphedPass):
+    def __init__(self, train_real, test_real, meta: dict, vocabs: Sequence, device, ops=None,
+                 target: Optional[str] = None, iters: int = 200, max_rows: int = 40000, graph: bool = False,
+                 cardinalities: Optional[Sequence[int]] = None):
+        """train_real / test_real: the real training and held-out rows as DataFrames, or already coded as float64
+        [m, n_cols] arrays.  cardinalities: categories per categorical column (in column order, the target
+        included), for coded arrays whose codes do not show them all."""
+        if meta.get("date_info"):
+            raise ValueError("DeviceUtility: the table has date columns; the decoded table holds their parts, not "
+                             "the dates, so rows would not be comparable")
+        self.device = torch.device(device)
+        if ops is None:
+            if self.device.type == "cuda":
+                from ..ops.hip import HipOps
+                ops = HipOps(self.device)
+            else:
+                from ..ops.ref import TorchOps
+                ops = TorchOps()
+        self.ops = ops
+        self.max_rows, self.iters = int(max_rows), int(iters)
+        if self.max_rows < 1 or self.iters < 0:
+            raise ValueError("DeviceUtility: max_rows must be >= 1 and iters >= 0")
+        self.names: List[str] = meta_column_names(meta)
+        self.n_cols = len(self.names)
+        self.target = str(target if target is not None else meta.get("target") or "")
+        is_cat = [c["type"] == CATEGORICAL for c in meta["columns"]]
+        if self.target not in self.names or not is_cat[self.names.index(self.target)]:
+            raise ValueError(f"DeviceUtility: the target {self.target!r} is not a categorical column of the table; "
+                             "regression targets are not supported")
+        tcol = self.names.index(self.target)
+        coded = []
+        for what, real in (("training", train_real), ("test", test_real)):
+            if isinstance(real, pd.DataFrame):
+                c = code_real_table(real, meta, vocabs)
+                if c.shape[0] != len(real):
+                    raise ValueError(f"DeviceUtility: the real {what} table lost rows in coding")
+            else:
+                c = np.ascontiguousarray(np.asarray(real, dtype=np.float64))
+                if c.ndim != 2 or c.shape[1] != self.n_cols:
+                    raise ValueError(f"DeviceUtility: expected a coded [m, {self.n_cols}] real {what} table, got "
+                                     f"{c.shape}")
+            if c.shape[0] < 1:
+                raise ValueError(f"DeviceUtility: the real {what} table is empty")
+            coded.append(c)
+        pooled = np.concatenate(coded, axis=0)
+        for j, cat in enumerate(is_cat):
+            col = pooled[:, j]
+            if not np.isfinite(col).all() or (cat and (col < 0).any()):
+                raise ValueError(f"DeviceUtility: the real column {self.names[j]!r} holds a value that is not a "
+                                 + ("category code" if cat else "finite number"))
+        cat_cols = [j for j, cat in enumerate(is_cat) if cat]
+        if cardinalities is not None and len(cardinalities) != len(cat_cols):
+            raise ValueError(f"DeviceUtility: cardinalities needs one entry per categorical column ({len(cat_cols)})")
+        card_all = []
+        for s, j in enumerate(cat_cols):
+            K = 1 + int(pooled[:, j].max())
+            if s < len(vocabs):
+                K = max(K, len(vocabs[s]))
+            if cardinalities is not None:
+                K = max(K, int(cardinalities[s]))
+            card_all.append(K)
+        self.K = card_all[cat_cols.index(tcol)]
+        kind, slot, card, feat_names = [], [], [], []
+        n_cont = 0
+        for j, cat in enumerate(is_cat):
+            if j == tcol:
+                kind.append(UTIL_TARGET)
+                slot.append(0)
+            elif cat:
+                kind.append(UTIL_CAT)
+                slot.append(len(card))
+                card.append(card_all[cat_cols.index(j)])
+                feat_names.append(self.names[j])
+            else:
+                kind.append(UTIL_CONT)
+                slot.append(n_cont)
+                n_cont += 1
+        self.kinds, self.n_cont, self.n_cat, self.card_list = kind, n_cont, len(card), card
+        offs = [0]
+        for Kc in card:
+            offs.append(offs[-1] + Kc + 1)
+        self.D = n_cont + offs[-1] + 1
+        if self.D > int(ops.UTIL_MAX_FEATURES) or self.K > int(ops.UTIL_MAX_CLASSES):
+            worst = sorted(range(len(card)), key=lambda s: -card[s])[:5]
+            raise ValueError(
+                f"DeviceUtility: {self.D} feature columns and {self.K} classes of the target {self.target!r}; the "
+                f"limits are UTIL_MAX_FEATURES = {int(ops.UTIL_MAX_FEATURES)} and UTIL_MAX_CLASSES = "
+                f"{int(ops.UTIL_MAX_CLASSES)}; the columns with the most categories are "
+                + ", ".join(f"{feat_names[s]!r} ({card[s]})" for s in worst))
+        cont_cols = [j for j, k in enumerate(kind) if k == UTIL_CONT]
+        mean = pooled[:, cont_cols].mean(axis=0) if cont_cols else np.zeros(0)
+        sd = pooled[:, cont_cols].std(axis=0) if cont_cols else np.zeros(0)
+        sd = np.where(sd > 0, sd, 1.0)
+        dev = self.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.kind = torch.tensor(kind, **i32)
+        self.slot = torch.tensor(slot, **i32)
+        self.card = torch.tensor(card, **i32)
+        self.offs = torch.tensor(offs, **i32)
+        self.mean = torch.tensor(mean, **f64)
+        self.sd = torch.tensor(sd, **f64)
+        self.betas = momentum_table(self.iters)
+        D, K = self.D, self.K
+        self.M, self.Minv = torch.zeros(D, D, **f64), torch.zeros(D, D, **f64)
+        self.Lt, self.X = torch.zeros(D, D, **f64), torch.zeros(D, D, **f64)
+        self.W, self.V, self.G = torch.zeros(D, K, **f64), torch.zeros(D, K, **f64), torch.zeros(D, K, **f64)
+        self.loss = torch.zeros(1, **f64)
+        self.conf = torch.zeros(K, K, **i32)
+        self.real = torch.zeros(2, **f64)
+        self.scores = torch.zeros(len(KEYS), **f64)
+        self.n_train, self.n_test = int(coded[0].shape[0]), int(coded[1].shape[0])
+        # the held-out rows are packed once; the real training rows are fitted once with the pass of score()
+        self.test = UtilityTable(self.n_test, n_cont, self.card, self.offs, D, K, dev)
+        ops.util_pack(torch.from_numpy(coded[1]).to(dev), self.kind, self.slot, self.mean, self.sd, self.test)
+        self._alloc(self.n_train)
+        self._launch(torch.from_numpy(coded[0]).to(dev), self.n_train)
+        self.real.copy_(self.scores[:2])
+        self.W_real, self.conf_real = self.W.clone(), self.conf.clone()
+        self.scores.zero_()
+        self._alloc(self.max_rows)
+        self.graph = bool(graph) and dev.type == "cuda"
+        self._graphs: Dict[Tuple[int, int], object] = {}
+        self._staged = None
+
+    def _alloc(self, rows: int) -> None:
+        dev, ops = self.device, self.ops
+        self.train = UtilityTable(rows, self.n_cont, self.card, self.offs, self.D, self.K, dev)
+        self.part = torch.zeros(max(ops.util_part(rows, self.D, self.K), 1), dtype=torch.float64, device=dev)
+        self.lossp = torch.zeros((rows + ops.UTIL_CHUNK - 1) // ops.UTIL_CHUNK, dtype=torch.float64, device=dev)
+
+    # ------------------------------------------------------------------ the pass
+    def _fit(self, values: torch.Tensor, n: int) -> None:
+        ops, t = self.ops, self.train
+        ops.util_pack(values, self.kind, self.slot, self.mean, self.sd, t)
+        ops.util_gram(t, n, self.M, self.part)
+        ops.util_factor(self.M, self.Lt, self.X, self.Minv)
+        self.W.zero_()
+        self.V.zero_()
+        for beta in self.betas:
+            ops.util_step(t, n, self.V, self.W, self.Minv, self.G, self.loss, self.part, self.lossp, beta)
+        ops.util_grad(t, n, self.W, self.G, self.loss, self.part, self.lossp)
+
+    def _launch(self, values: torch.Tensor, n: int) -> None:
+        self._fit(values, n)
+        self.ops.util_predict(self.test, self.n_test, self.train.counts, self.W, self.conf, self.G, self.loss,
+                              self.real, self.scores)
+
+    def score(self, values: torch.Tensor) -> UtilityScores:
+        """values: [n, n_cols] float64 on the evaluator's device, as ``generate_decoded`` returns them (finite
+        values in the continuous columns are a precondition).  The work is queued on the current stream; the
+        returned scores are device tensors and nothing waits for them."""
+        if values.dim() != 2 or values.shape[1] != self.n_cols or values.dtype != torch.float64:
+            raise ValueError(f"score: expected a float64 [n, {self.n_cols}] table, got {tuple(values.shape)} "
+                             f"{values.dtype}")
+        if values.device != self.scores.device:
+            raise ValueError(f"score: the table is on {values.device}, the evaluator on {self.scores.device}")
+        n = int(values.shape[0])
+        if n < 1 or n > self.max_rows:
+            raise ValueError(f"score: {n} rows; this evaluator's buffers hold 1..{self.max_rows}")
+        values = values.contiguous()
+        if self.graph:
+            self._replay(values, n)
+        else:
+            self._launch(values, n)
+        return UtilityScores(self.scores.clone(), self.conf.clone(), self.W.clone())

@@ -61,6 +61,7 @@ class LoadedGenerator:
     _similarity: dict = dataclasses.field(default_factory=dict, repr=False)   # (real table, n) -> its evaluator
     _privacy: dict = dataclasses.field(default_factory=dict, repr=False)      # the same for privacy()
     _correlation: dict = dataclasses.field(default_factory=dict, repr=False)  # and for correlation()
+    _utility: dict = dataclasses.field(default_factory=dict, repr=False)      # and for utility()
 
     def sample(self, n: int, where=None, max_passes: int = 64) -> np.ndarray:
         """[n, n_columns] decoded values (label codes for categoricals), float64.  A GPU table comes
@@ -115,16 +116,47 @@ class LoadedGenerator:
                                   where=where, max_passes=max_passes)[:2]
 
     def write_csv_all(self, path: str, n: int, score_real=None, privacy_real=None, corr_real=None, threads: int = 0,
-                      where=None, max_passes: int = 64):
-        """:meth:`write_csv` with whichever of :meth:`score` (score_real), :meth:`privacy` (privacy_real) and
-        :meth:`correlation` (corr_real) are asked for, all of the rows the CSV holds and all taken on the device
-        before the copy.  Returns ((Avg_JSD, Avg_WD) | None, privacy dict | None, correlation dict | None)."""
+                      where=None, max_passes: int = 64, utility_real=None, utility_test=None, utility_iters: int = 200):
+        """:meth:`write_csv` with whichever of :meth:`score` (score_real), :meth:`privacy` (privacy_real),
+        :meth:`correlation` (corr_real) and :meth:`utility` (utility_real, utility_test) are asked for, all of the
+        rows the CSV holds and all taken on the device before the copy.  Returns ((Avg_JSD, Avg_WD) | None, privacy
+        dict | None, correlation dict | None, utility dict | None)."""
         vals = self.device_table(n, where=where, max_passes=max_passes)
         sim = self._evaluator(score_real, n).score(vals) if score_real is not None else None
         priv = self._privacy_evaluator(privacy_real, n).score(vals) if privacy_real is not None else None
         corr = self._correlation_evaluator(corr_real, n).score(vals) if corr_real is not None else None
+        util = None
+        if utility_real is not None:
+            util = self._utility_evaluator(utility_real, utility_test, n, utility_iters).score(vals)
         self._write_values(path, self._to_host(vals), threads)
-        return tuple(s.floats() if s is not None else None for s in (sim, priv, corr))
+        return tuple(s.floats() if s is not None else None for s in (sim, priv, corr, util))
+
+    def utility(self, train_real, test_real=None, n: int = 40000, where=None, max_passes: int = 64,
+                iters: int = 200) -> dict:
+        """ML utility of n generated rows (eval/utility_device.py): a class-balanced logistic regression is fitted
+        on them on the engine's device and tested on real rows; ``f1_fake`` / ``acc_fake`` against ``f1_real`` /
+        ``acc_real`` of the same fit on ``train_real``, their gaps, and ``loss_fake`` / ``grad_fake`` of the fit.
+        The tables are DataFrames or CSV paths; without ``test_real`` the rows of ``train_real`` with ``index % 5
+        == 4`` are held out and the rest are the training rows.  The evaluator is kept per tables, n and iters."""
+        return self._utility_evaluator(train_real, test_real, n, iters).score(
+            self.device_table(n, where=where, max_passes=max_passes)).floats()
+
+    def _utility_evaluator(self, train_real, test_real, n: int, iters: int = 200):
+        import pandas as pd
+        from ..eval.utility_device import DeviceUtility
+        key = tuple(t if isinstance(t, str) or t is None else id(t) for t in (train_real, test_real)) + (int(n),
+                                                                                                       int(iters))
+        if key not in self._utility:
+            train = pd.read_csv(train_real) if isinstance(train_real, str) else train_real
+            test = pd.read_csv(test_real) if isinstance(test_real, str) else test_real
+            frames = (train, test)
+            if test is None:
+                held = np.arange(len(train)) % 5 == 4
+                train, test = train[~held].reset_index(drop=True), train[held].reset_index(drop=True)
+            self._utility.clear()
+            self._utility[key] = (frames, DeviceUtility(train, test, self.meta, self.vocabs, self.engine.device,
+                                                        ops=self.engine.ops, iters=int(iters), max_rows=int(n)))
+        return self._utility[key][1]
 
     def correlation(self, real, n: int = 40000, where=None, max_passes: int = 64) -> dict:
         """Diff. Corr. of n generated rows against ``real`` (a DataFrame or a CSV path): generated and scored on the

@@ -694,3 +694,48 @@ class HipOps:
     def corr_diff(self, A, B, out):
         """Same contract as TorchOps.corr_diff."""
         self.L.corr_diff(A, B, out)
+
+    # ------------------------------------------------------------------ ML-utility evaluator (kernels/utility.hip)
+    UTIL_CONT, UTIL_CAT, UTIL_TARGET = 0, 1, 2
+    UTIL_MAX_FEATURES = 1024     # kernels/launch.h: D, one lane of the factorisation per column
+    UTIL_MAX_CLASSES = 64        # K: a block of 64 rows of logits in LDS
+    UTIL_CHUNK = 128             # rows per chunk (a row group is a whole number of them)
+
+    @staticmethod
+    def util_part(n_max: int, D: int, K: int) -> int:
+        """float64 scratch elements util_gram / util_grad need for any table of up to n_max rows"""
+        return int(native.require().util_part(int(n_max), int(D), int(K)))
+
+    @staticmethod
+    def util_groups(n: int, cells: int) -> int:
+        """row groups (partials of ``cells`` doubles each) a product over n rows is split into"""
+        return int(native.require().util_groups(int(n), int(cells)))
+
+    @staticmethod
+    def _util_table(t, n):
+        return (t.cont, t.cat_t, t.y, t.s, t.counts, t.info, t.card, t.offs, int(n))
+
+    def util_pack(self, values, kind, slot, mean, sd, tab):
+        """Same contract as TorchOps.util_pack."""
+        self.L.util_pack(values, kind, slot, tab.card, tab.offs, mean, sd, int(tab.D), tab.cont, tab.cat_t, tab.y,
+                         tab.s, tab.counts, tab.info)
+
+    def util_gram(self, tab, n, M, part):
+        """Same contract as TorchOps.util_gram; part: float64 [>= util_part(n, D, K)]."""
+        self.L.util_gram(*self._util_table(tab, n), M, part)
+
+    def util_factor(self, M, Lt, X, Minv):
+        """Same contract as TorchOps.util_factor; Lt, X: float64 [D, D] scratch."""
+        self.L.util_factor(M, Lt, X, Minv)
+
+    def util_grad(self, tab, n, P, G, loss, part, lossp):
+        """Same contract as TorchOps.util_grad; lossp: float64 [>= util_groups(n, D K)]."""
+        self.L.util_grad(*self._util_table(tab, n), P, G, loss, part, lossp)
+
+    def util_step(self, tab, n, V, W, Minv, G, loss, part, lossp, beta):
+        """Same contract as TorchOps.util_step."""
+        self.L.util_step(*self._util_table(tab, n), V, W, Minv, G, loss, part, lossp, float(beta))
+
+    def util_predict(self, tab, n, train_counts, W, conf, G, loss, real, out):
+        """Same contract as TorchOps.util_predict."""
+        self.L.util_predict(*self._util_table(tab, n), train_counts, W, conf, G, loss, real, out)

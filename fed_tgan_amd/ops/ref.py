@@ -736,3 +736,162 @@ class TorchOps:
         off.fill_diagonal_(0.0)
         out[1] = off.sum() / (C * (C - 1)) if C > 1 else 0.0
         out[2] = off.max() if C > 1 else 0.0
+
+    # ------------------------------------------------------------------ ML-utility evaluator
+    UTIL_CONT, UTIL_CAT, UTIL_TARGET = 0, 1, 2
+    UTIL_MAX_FEATURES, UTIL_MAX_CLASSES, UTIL_CHUNK = 1024, 64, 128    # the HIP kernels' limits; shared attributes only
+
+    @staticmethod
+    def util_part(n_max: int, D: int, K: int) -> int:
+        return 1
+
+    @staticmethod
+    def util_groups(n: int, cells: int) -> int:
+        return 1
+
+    def util_pack(self, values, kind, slot, mean, sd, tab):
+        """One pass over a decoded table values [n, n_cols] float64 into the packed table ``tab``
+        (eval/utility_device.py UtilityTable).  kind / slot int32 [n_cols]: a continuous column (UTIL_CONT) becomes
+        column slot of tab.cont as (v - mean[slot]) / sd[slot]; a categorical feature (UTIL_CAT) row slot of tab.cat_t,
+        its code when it lies in [0, card[slot]), else the overflow bin card[slot]; the target (UTIL_TARGET) tab.y, its
+        code or K.  tab.counts [K] = rows per class, tab.s = n_valid / (present * count[y]) per row (0 where y == K),
+        tab.info = [n_valid, classes present, S = sum_c count_c w_c (1 when that is 0), 0]."""
+        n, K, dev = values.shape[0], tab.K, values.device
+        kl, sl = kind.tolist(), slot.tolist()
+        cc = [c for c, k in enumerate(kl) if k == self.UTIL_CONT]
+        kc = [c for c, k in enumerate(kl) if k == self.UTIL_CAT]
+        tc = [c for c, k in enumerate(kl) if k == self.UTIL_TARGET]
+        if cc:
+            cs = torch.tensor([sl[c] for c in cc], dtype=torch.long, device=dev)
+            v = values[:, torch.tensor(cc, dtype=torch.long, device=dev)]
+            tab.cont[:n, cs] = (v - mean[cs][None, :]) / sd[cs][None, :]
+        if kc:
+            ks = torch.tensor([sl[c] for c in kc], dtype=torch.long, device=dev)
+            v = values[:, torch.tensor(kc, dtype=torch.long, device=dev)]
+            Kc = tab.card[ks].to(torch.float64)[None, :]
+            ok = (v >= 0) & (v < Kc)
+            tab.cat_t[ks, :n] = torch.where(ok, v, Kc.expand_as(v)).t().to(tab.cat_t.dtype)
+        v = values[:, tc[0]]
+        ok = (v >= 0) & (v < K)
+        y = torch.where(ok, v, torch.full_like(v, float(K))).long()
+        tab.y[:n] = y.to(tab.y.dtype)
+        counts = torch.bincount(y, minlength=K + 1)[:K]
+        tab.counts.copy_(counts.to(tab.counts.dtype))
+        cd = counts.to(torch.float64)
+        nv, present = cd.sum(), (counts > 0).sum().to(torch.float64)
+        live = counts > 0
+        cw = torch.where(live, nv / (present * torch.where(live, cd, torch.ones_like(cd))), torch.zeros_like(cd))
+        S = (cd * cw).sum()
+        tab.info[0], tab.info[1], tab.info[3] = nv, present, 0.0
+        tab.info[2] = torch.where(S > 0, S, torch.ones_like(S))
+        tab.s[:n] = torch.cat([cw, cw.new_zeros(1)])[y]
+
+    @staticmethod
+    def _util_codes(tab, n):
+        return [tab.cat_t[c, :n].long().clamp(0, K) for c, K in enumerate(tab.card.tolist())]
+
+    def util_gram(self, tab, n, M, part=None):
+        """M [D, D] = (F^T diag(s) F / 2 + diag(reg)) / S with F = [cont | one-hot(codes) | 1], reg = 1 but for the
+        last (intercept) row's 0.  The one-hot blocks are never built: a block of the product is the weighted
+        contingency table of two columns, or the rows of s X added into the bins a column's codes select."""
+        D, nc = tab.D, tab.cont.shape[1]
+        X, s = tab.cont[:n], tab.s[:n]
+        G = torch.zeros(D, D, dtype=torch.float64, device=M.device)
+        sX = X * s[:, None]
+        G[:nc, :nc] = X.t() @ sX
+        G[D - 1, D - 1] = s.sum()
+        G[:nc, D - 1] = G[D - 1, :nc] = sX.sum(dim=0)
+        codes, cl, ol = self._util_codes(tab, n), tab.card.tolist(), tab.offs.tolist()
+        for a, ca in enumerate(codes):
+            ia, ka = nc + ol[a], cl[a] + 1
+            blk = torch.zeros(ka, nc, dtype=torch.float64, device=M.device).index_add_(0, ca, sX)
+            G[ia:ia + ka, :nc] = blk
+            G[:nc, ia:ia + ka] = blk.t()
+            G[ia:ia + ka, D - 1] = G[D - 1, ia:ia + ka] = torch.bincount(ca, weights=s, minlength=ka)
+            for b in range(a, len(codes)):
+                ib, kb = nc + ol[b], cl[b] + 1
+                T = torch.bincount(ca * kb + codes[b], weights=s, minlength=ka * kb).view(ka, kb)
+                G[ia:ia + ka, ib:ib + kb] = T
+                G[ib:ib + kb, ia:ia + ka] = T.t()
+        reg = torch.ones(D, dtype=torch.float64, device=M.device)
+        reg[D - 1] = 0.0
+        M.copy_((0.5 * G + torch.diag(reg)) / tab.info[2])
+
+    def util_factor(self, M, Lt=None, X=None, Minv=None):
+        """Minv = (M + 1e-10 trace(M) / D I)^-1 through the Cholesky factor (LAPACK on the host)."""
+        D = M.shape[0]
+        A = M.detach().cpu()
+        A = A + torch.eye(D, dtype=torch.float64) * (1e-10 * torch.trace(A) / D)
+        Minv.copy_(torch.cholesky_inverse(torch.linalg.cholesky(A)).to(M.device))
+
+    def _util_logits(self, tab, n, P, codes):
+        nc, ol = tab.cont.shape[1], tab.offs.tolist()
+        Z = tab.cont[:n] @ P[:nc] + P[tab.D - 1][None, :]
+        for c, code in enumerate(codes):
+            Z = Z + P[nc + ol[c] + code]
+        return Z
+
+    def util_grad(self, tab, n, P, G, loss, part=None, lossp=None):
+        """G [D, K] = grad f(P) and loss[0] = f(P) of f(P) = (sum_i s_i CE(softmax(F_i P), y_i) + |P without its
+        last row|^2 / 2) / S; the softmax runs over the classes with counts > 0, the others get probability 0."""
+        D, K, nc = tab.D, tab.K, tab.cont.shape[1]
+        codes, cl, ol = self._util_codes(tab, n), tab.card.tolist(), tab.offs.tolist()
+        Z = self._util_logits(tab, n, P, codes)
+        s, y = tab.s[:n], tab.y[:n].long()
+        pres = (tab.counts > 0)[None, :]
+        neg = torch.full_like(Z, float("-inf"))
+        mx = torch.where(pres, Z, neg).max(dim=1).values
+        mx = torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))
+        E = torch.where(pres, torch.exp(Z - mx[:, None]), torch.zeros_like(Z))
+        den = E.sum(dim=1)
+        den = torch.where(den > 0, den, torch.ones_like(den))
+        yv = y.clamp(0, K - 1)
+        Y = torch.zeros_like(Z).scatter_(1, yv[:, None], 1.0)
+        R = s[:, None] * (E / den[:, None] - Y)
+        rows = s * (torch.log(den) + mx - Z.gather(1, yv[:, None])[:, 0])
+        rows = torch.where(s > 0, rows, torch.zeros_like(rows))
+        R = torch.where((s > 0)[:, None], R, torch.zeros_like(R))
+        g = torch.zeros(D, K, dtype=torch.float64, device=P.device)
+        g[:nc] = tab.cont[:n].t() @ R
+        g[D - 1] = R.sum(dim=0)
+        for c, code in enumerate(codes):
+            g[nc + ol[c]:nc + ol[c] + cl[c] + 1] = torch.zeros(cl[c] + 1, K, dtype=torch.float64,
+                                                               device=P.device).index_add_(0, code, R)
+        g[:D - 1] += P[:D - 1]
+        S = tab.info[2]
+        loss[0] = (rows.sum() + 0.5 * (P[:D - 1] * P[:D - 1]).sum()) / S
+        G.copy_(g / S)
+
+    def util_step(self, tab, n, V, W, Minv, G, loss, part=None, lossp=None, beta=0.0):
+        """One accelerated step: G = grad f(V); W' = V - Minv G; V' = W' + beta (W' - W)."""
+        self.util_grad(tab, n, V, G, loss)
+        wn = V - Minv @ G
+        V.copy_(wn + float(beta) * (wn - W))
+        W.copy_(wn)
+
+    def util_predict(self, tab, n, train_counts, W, conf, G, loss, real, out):
+        """conf [K, K] int32: rows of ``tab`` by (target code, predicted class), the prediction being the largest
+        logit over the classes with train_counts > 0 (the lowest such class on a tie), rows whose target is no code
+        skipped.  out[0..7] = weighted F1, accuracy, real[0], real[1], real[0] - F1, real[1] - accuracy, loss[0],
+        max |G|."""
+        K = tab.K
+        Z = self._util_logits(tab, n, W, self._util_codes(tab, n))
+        pres = (train_counts > 0)[None, :]
+        Zm = torch.where(pres, Z, torch.full_like(Z, float("-inf")))
+        mx = Zm.max(dim=1).values
+        idx = torch.arange(K, device=Z.device)[None, :].expand_as(Z)
+        pred = torch.where(Zm == mx[:, None], idx, torch.full_like(idx, K)).min(dim=1).values.clamp(max=K - 1)
+        y = tab.y[:n].long()
+        ok = (y >= 0) & (y < K)
+        c = torch.bincount(y[ok] * K + pred[ok], minlength=K * K).view(K, K)
+        conf.copy_(c.to(conf.dtype).view(conf.shape))
+        cd = c.to(torch.float64)
+        rs, cs, tp = cd.sum(dim=1), cd.sum(dim=0), torch.diagonal(cd)
+        den = rs + cs
+        f = torch.where(den > 0, 2.0 * tp / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
+        total = rs.sum()
+        safe = torch.where(total > 0, total, torch.ones_like(total))
+        f1 = torch.where(total > 0, (rs * f).sum() / safe, torch.zeros_like(total))
+        acc = torch.where(total > 0, tp.sum() / safe, torch.zeros_like(total))
+        out[0], out[1], out[2], out[3] = f1, acc, real[0], real[1]
+        out[4], out[5], out[6], out[7] = real[0] - f1, real[1] - acc, loss[0], G.abs().max()
