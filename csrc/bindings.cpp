@@ -1567,6 +1567,149 @@ int64_t util_chunk() { return fedtgan::UTIL_CHUNK; }
 int64_t util_part(int64_t n_max, int64_t D, int64_t K) { return fedtgan::util_part_doubles(n_max, D, K); }
 int64_t util_groups(int64_t n, int64_t cells) { return fedtgan::util_groups(n, cells).groups; }
 
+// ----------------------------------------------------------------------------- tree-utility evaluator
+namespace {
+bool tree_u8(const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kByte && t.is_contiguous(); }
+
+// a binned table: bins uint8 [F, ld >= n], y int32 [>= n], counts int32 [K], cw float64 [K]
+fedtgan::TreeTable tree_table(const char* what, const Tensor& bins, const Tensor& y, const Tensor& counts,
+                              const Tensor& cw, int64_t n) {
+  TORCH_CHECK(n >= 1 && n < (int64_t)INT32_MAX, what, ": n");
+  TORCH_CHECK(tree_u8(bins) && bins.dim() == 2 && bins.size(0) >= 1 && bins.size(0) <= fedtgan::TREE_MAX_FEATURES &&
+                  bins.size(1) >= n, what, ": bins uint8 [1 <= F <= TREE_MAX_FEATURES, >= n]");
+  const int64_t K = cw.numel();
+  TORCH_CHECK(sim_i32(y) && y.numel() >= n && sim_i32(counts) && counts.numel() == K && sim_f64(cw) && K >= 1 &&
+                  K <= fedtgan::TREE_MAX_CLASSES, what, ": y int32 [>= n], counts int32 [K], cw float64 [K <= 64]");
+  fedtgan::TreeTable t{};
+  t.bins = bins.data_ptr<uint8_t>();
+  t.y = y.data_ptr<int>();
+  t.counts = counts.data_ptr<int>();
+  t.cw = cw.data_ptr<double>();
+  t.ld = bins.size(1);
+  t.n = (int)n;
+  t.F = (int)bins.size(0);
+  t.K = (int)K;
+  return t;
+}
+
+void tree_check_nodes(const char* what, const Tensor& feature, const Tensor& bin, const Tensor& left,
+                      const Tensor& counts, int64_t K) {
+  TORCH_CHECK(sim_i32(feature) && feature.dim() == 2 && feature.size(0) >= 1 && feature.size(0) <= 65535 &&
+                  feature.size(1) >= 1, what, ": feature int32 [T <= 65535, cap]");
+  for (const Tensor* t : {&bin, &left})
+    TORCH_CHECK(sim_i32(*t) && t->sizes() == feature.sizes(), what, ": bin / left int32 [T, cap]");
+  TORCH_CHECK(sim_i32(counts) && counts.dim() == 3 && counts.size(0) == feature.size(0) &&
+                  counts.size(1) == feature.size(1) && counts.size(2) == K, what, ": counts int32 [T, cap, K]");
+}
+}  // namespace
+
+void tree_pack(const Tensor& values, const Tensor& kind, const Tensor& slot, const Tensor& card, const Tensor& edges,
+               const Tensor& eoff, const Tensor& bins, const Tensor& y, const Tensor& counts, const Tensor& cw) {
+  TORCH_CHECK(sim_f64(values) && values.dim() == 2 && values.size(0) >= 1 && values.size(1) >= 2,
+              "tree_pack: values must be contiguous float64 [rows >= 1, n_cols >= 2]");
+  TORCH_CHECK(values.numel() < (int64_t)INT32_MAX, "tree_pack: a table holds fewer than 2^31 values");
+  TORCH_CHECK(sim_i32(kind) && sim_i32(slot) && kind.numel() == values.size(1) && slot.numel() == values.size(1),
+              "tree_pack: int32 kind / slot, one entry per column");
+  fedtgan::TreePackArgs a{};
+  a.t = tree_table("tree_pack", bins, y, counts, cw, values.size(0));
+  TORCH_CHECK(bins.size(0) + 1 == values.size(1), "tree_pack: F + 1 must be n_cols");
+  TORCH_CHECK(sim_i32(card) && card.numel() == a.t.F && sim_i32(eoff) && eoff.numel() == a.t.F + 1 && sim_f64(edges),
+              "tree_pack: card int32 [F], eoff int32 [F + 1], edges float64");
+  a.values = values.data_ptr<double>();
+  a.n_cols = (int)values.size(1);
+  a.kind = kind.data_ptr<int>();
+  a.slot = slot.data_ptr<int>();
+  a.card = card.data_ptr<int>();
+  a.edges = edges.numel() ? edges.data_ptr<double>() : nullptr;
+  a.eoff = eoff.data_ptr<int>();
+  a.n_edges = (int)edges.numel();
+  fedtgan::launch_tree_pack(a, cur_stream());
+}
+
+void tree_bootstrap(const Tensor& mult, int64_t n, bool bootstrap, int64_t seed) {
+  TORCH_CHECK(sim_i32(mult) && mult.dim() == 2 && mult.size(0) >= 1 && mult.size(0) <= 65535 && n >= 1 &&
+                  mult.size(1) >= n && n < (int64_t)INT32_MAX, "tree_bootstrap: mult int32 [T <= 65535, >= n]");
+  fedtgan::launch_tree_bootstrap(mult.data_ptr<int>(), (int)mult.size(0), mult.size(1), (int)n, bootstrap ? 1 : 0,
+                                 (uint64_t)seed, cur_stream());
+}
+
+void tree_grow(const Tensor& bins, const Tensor& y, const Tensor& tcounts, const Tensor& cw, const Tensor& nbins,
+               int64_t max_bins, int64_t n, const Tensor& mult, const Tensor& rows, const Tensor& feature,
+               const Tensor& bin, const Tensor& left, const Tensor& heap, const Tensor& counts, const Tensor& seg,
+               const Tensor& level, const Tensor& lcounts, int64_t max_depth, int64_t min_leaf, int64_t m_feat,
+               int64_t seed) {
+  fedtgan::TreeGrowArgs a{};
+  a.t = tree_table("tree_grow", bins, y, tcounts, cw, n);
+  const int64_t K = a.t.K, F = a.t.F;
+  tree_check_nodes("tree_grow", feature, bin, left, counts, K);
+  const int64_t T = feature.size(0), cap = feature.size(1);
+  TORCH_CHECK(sim_i32(heap) && heap.sizes() == feature.sizes() && sim_i32(seg) && seg.numel() == 2 * T * cap &&
+                  sim_i32(level) && level.numel() == 4 * T,
+              "tree_grow: heap int32 [T, cap], seg int32 [T, cap, 2], level int32 [T, 4]");
+  TORCH_CHECK(sim_i32(mult) && mult.dim() == 2 && mult.size(0) == T && mult.size(1) >= n && sim_i32(rows) &&
+                  rows.numel() == 2 * mult.numel(), "tree_grow: mult int32 [T, ldr >= n], rows int32 [2, T, ldr]");
+  TORCH_CHECK(sim_i32(lcounts) && lcounts.dim() == 3 && lcounts.size(0) == T && lcounts.size(1) >= 1 &&
+                  lcounts.size(2) == K, "tree_grow: lcounts int32 [T, lvl_cap, K]");
+  TORCH_CHECK(sim_i32(nbins) && nbins.numel() == F && max_bins >= 1 && max_bins <= fedtgan::TREE_MAX_BINS,
+              "tree_grow: nbins int32 [F], max_bins <= TREE_MAX_BINS");
+  TORCH_CHECK(max_depth >= 0 && max_depth <= fedtgan::TREE_MAX_DEPTH && min_leaf >= 1 && min_leaf < (int64_t)INT32_MAX &&
+                  m_feat >= 1, "tree_grow: 0 <= max_depth <= TREE_MAX_DEPTH, min_leaf >= 1, m_feat >= 1");
+  a.nbins = nbins.data_ptr<int>();
+  a.mult = mult.data_ptr<int>();
+  a.rows = rows.data_ptr<int>();
+  a.feature = feature.data_ptr<int>();
+  a.bin = bin.data_ptr<int>();
+  a.left = left.data_ptr<int>();
+  a.heap = heap.data_ptr<int>();
+  a.counts = counts.data_ptr<int>();
+  a.seg = seg.data_ptr<int>();
+  a.level = level.data_ptr<int>();
+  a.lcounts = lcounts.data_ptr<int>();
+  a.ldr = mult.size(1);
+  a.T = (int)T;
+  a.cap = (int)cap;
+  a.lvl_cap = (int)lcounts.size(1);
+  a.max_depth = (int)max_depth;
+  a.min_leaf = (int)min_leaf;
+  a.m_feat = (int)(m_feat < F ? m_feat : F);
+  a.hist_bytes = (int)((max_bins * K * 4 + 7) / 8 * 8);
+  a.seed = (uint64_t)seed;
+  fedtgan::launch_tree_grow(a, cur_stream());
+}
+
+void tree_predict(const Tensor& bins, const Tensor& y, const Tensor& tcounts, const Tensor& cw, int64_t n,
+                  const Tensor& feature, const Tensor& bin, const Tensor& left, const Tensor& counts, bool soft,
+                  const Tensor& conf) {
+  fedtgan::TreePredictArgs a{};
+  a.t = tree_table("tree_predict", bins, y, tcounts, cw, n);
+  tree_check_nodes("tree_predict", feature, bin, left, counts, a.t.K);
+  TORCH_CHECK(sim_i32(conf) && conf.numel() == (int64_t)a.t.K * a.t.K, "tree_predict: conf int32 [K, K]");
+  TORCH_CHECK(soft || feature.size(0) == 1, "tree_predict: the hard vote is one tree's");
+  a.feature = feature.data_ptr<int>();
+  a.bin = bin.data_ptr<int>();
+  a.left = left.data_ptr<int>();
+  a.counts = counts.data_ptr<int>();
+  a.T = (int)feature.size(0);
+  a.cap = (int)feature.size(1);
+  a.soft = soft ? 1 : 0;
+  a.conf = conf.data_ptr<int>();
+  fedtgan::launch_tree_predict(a, cur_stream());
+}
+
+void tree_scores(const Tensor& conf, const Tensor& real, const Tensor& out) {
+  TORCH_CHECK(sim_i32(conf) && conf.dim() == 2 && conf.size(0) == conf.size(1) && conf.size(0) >= 1 &&
+                  conf.size(0) <= fedtgan::TREE_MAX_CLASSES, "tree_scores: conf int32 [K, K]");
+  TORCH_CHECK(sim_f64(real) && real.numel() >= 2 && sim_f64(out) && out.numel() >= 6,
+              "tree_scores: real [2], out [6] float64");
+  fedtgan::launch_tree_scores(conf.data_ptr<int>(), (int)conf.size(0), real.data_ptr<double>(), out.data_ptr<double>(),
+                              cur_stream());
+}
+
+int64_t tree_max_bins() { return fedtgan::TREE_MAX_BINS; }
+int64_t tree_max_classes() { return fedtgan::TREE_MAX_CLASSES; }
+int64_t tree_max_depth() { return fedtgan::TREE_MAX_DEPTH; }
+int64_t tree_max_features() { return fedtgan::TREE_MAX_FEATURES; }
+
 // ----------------------------------------------------------------------------- native RCCL plane (csrc/comm)
 void rccl_load_op(const std::string& path) { fedtgan::comm::rccl_load(path); }
 
@@ -1778,7 +1921,8 @@ void vgm_fit(const Tensor& x, const Tensor& n_rows, const c10::optional<Tensor>&
 int64_t check_status() {
   (void)hipDeviceSynchronize();
   return (int64_t)(fedtgan::check_status_gemm() | fedtgan::check_status_ctgan_ops() | fedtgan::check_status_vgm() |
-                   fedtgan::check_status_cond_gen() | fedtgan::check_status_similarity());
+                   fedtgan::check_status_cond_gen() | fedtgan::check_status_similarity() |
+                   fedtgan::check_status_forest());
 }
 
 #ifdef FEDTGAN_CHECKED
@@ -2081,6 +2225,17 @@ TORCH_LIBRARY(fedtgan, m) {
   m.def("util_chunk() -> int", &util_chunk);
   m.def("util_part(int n_max, int D, int K) -> int", &util_part);
   m.def("util_groups(int n, int cells) -> int", &util_groups);
+  m.def("tree_pack(Tensor values, Tensor kind, Tensor slot, Tensor card, Tensor edges, Tensor eoff, Tensor(a!) bins, Tensor(b!) y, Tensor(c!) counts, Tensor(d!) cw) -> ()");
+  m.def("tree_bootstrap(Tensor(a!) mult, int n, bool bootstrap, int seed) -> ()");
+  m.def(
+      "tree_grow(Tensor bins, Tensor y, Tensor tcounts, Tensor cw, Tensor nbins, int max_bins, int n, Tensor mult, Tensor(a!) rows, Tensor(b!) feature, Tensor(c!) bin, Tensor(d!) left, Tensor(e!) heap, Tensor(f!) counts, "
+      "Tensor(g!) seg, Tensor(h!) level, Tensor(i!) lcounts, int max_depth, int min_leaf, int m_feat, int seed) -> ()");
+  m.def("tree_predict(Tensor bins, Tensor y, Tensor tcounts, Tensor cw, int n, Tensor feature, Tensor bin, Tensor left, Tensor counts, bool soft, Tensor(a!) conf) -> ()");
+  m.def("tree_scores(Tensor conf, Tensor real, Tensor(a!) out) -> ()");
+  m.def("tree_max_bins() -> int", &tree_max_bins);
+  m.def("tree_max_classes() -> int", &tree_max_classes);
+  m.def("tree_max_depth() -> int", &tree_max_depth);
+  m.def("tree_max_features() -> int", &tree_max_features);
   m.def(
       "vgm_estep(Tensor x, Tensor n_rows, Tensor consts, Tensor means, Tensor prec, Tensor(a!) partial, "
       "int rows_per_block) -> ()");
@@ -2156,6 +2311,11 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("util_grad", &util_grad);
   m.impl("util_step", &util_step);
   m.impl("util_predict", &util_predict);
+  m.impl("tree_pack", &tree_pack);
+  m.impl("tree_bootstrap", &tree_bootstrap);
+  m.impl("tree_grow", &tree_grow);
+  m.impl("tree_predict", &tree_predict);
+  m.impl("tree_scores", &tree_scores);
   m.impl("vgm_encode", &vgm_encode);
   m.impl("vgm_estep", &vgm_estep);
   m.impl("kmeans_step", &kmeans_step);

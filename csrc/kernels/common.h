@@ -30,6 +30,7 @@ enum CheckCode : unsigned {
   CHK_ENCODE_LUT = 6,    // encode: label lookup outside the table
   CHK_COND_REQUEST = 7,  // conditional generation: bin / span / option / column / segment row outside its table
   CHK_SIM_CODE = 8,      // similarity evaluator: categorical code outside [0, vocab)
+  CHK_TREE_INDEX = 9,    // tree evaluator: bin / class / row-list entry / node index outside its table
 };
 #ifdef FEDTGAN_CHECKED
 #define FT_CHECK(flag, cond, code)                                  \

@@ -671,6 +671,72 @@ void launch_util_update(double* V, double* W, const double* Minv, const double* 
 void launch_util_predict(const UtilTable& t, const int* train_counts, const double* W, int* conf, const double* G,
                          const double* loss, const double* real, double* out, hipStream_t stream);
 
+// Tree-utility evaluator (kernels/forest.hip): a histogram decision tree and a random forest fitted on the binned
+// decoded table, and their confusion matrices on held-out rows (eval/forest_device.py has the definition).  Counting
+// is in integers, the criterion is fp64 in a fixed order without contraction, so a fit is bit-identical on every run.
+// The limits: a bin is one byte; the [bins, K] uint32 histogram of one (node, feature) lives in LDS (64 KiB at both
+// limits, against 160 KiB per CU); heap indices below 2^21 fit the Philox counter word they key.
+constexpr int TREE_MAX_BINS = 256;          // bins of a feature, the overflow / NaN bin of a categorical one included
+constexpr int TREE_MAX_CLASSES = 64;        // K: categories of the target column
+constexpr int TREE_MAX_DEPTH = 20;
+constexpr int TREE_MAX_FEATURES = 1024;     // per-feature candidates of a node in LDS (20 B each)
+enum TreeKind : int { TREE_CONT = 0, TREE_CAT = 1, TREE_TARGET = 2 };
+unsigned check_status_forest();
+// a binned table
+struct TreeTable {
+  uint8_t* bins;          // [F, ld] feature-major
+  int* y;                 // [>= n] target code, K where the value is no code of [0, K)
+  int* counts;            // [K] valid rows per class
+  double* cw;             // [K] balanced class weights, 0 for an absent class
+  int64_t ld;
+  int n, F, K;
+};
+struct TreePackArgs {
+  const double* values;   // [n, n_cols] decoded table, row-major
+  int n_cols;
+  const int* kind;        // [n_cols] TreeKind
+  const int* slot;        // [n_cols] feature index
+  const int* card;        // [F] categories of a categorical feature (0 for a continuous one)
+  const double* edges;    // ascending distinct edges of the continuous features
+  const int* eoff;        // [F + 1] a feature's edges are edges[eoff[f] .. eoff[f + 1])
+  int n_edges;
+  TreeTable t;
+};
+void launch_tree_pack(const TreePackArgs& a, hipStream_t stream);
+// mult [T, ldr]: 1 per row, or (bootstrap) how often tree t drew the row among its n draws
+void launch_tree_bootstrap(int* mult, int T, int64_t ldr, int n, int bootstrap, uint64_t seed, hipStream_t stream);
+// the trees of one model and the scratch of their growth
+struct TreeGrowArgs {
+  TreeTable t;
+  const int* nbins;       // [F] bins of a feature (< 2: never a candidate)
+  const int* mult;        // [T, ldr]
+  int* rows;              // [2, T, ldr] ping-pong row lists: a node's rows are a segment, in ascending row order
+  int* feature;           // [T, cap] -1 for a leaf
+  int* bin;               // [T, cap]
+  int* left;              // [T, cap] the right child is left + 1
+  int* heap;              // [T, cap] root 1, children 2 g and 2 g + 1; 0 for an unused slot
+  int* counts;            // [T, cap, K] class counts, multiplicities included
+  int* seg;               // [T, cap, 2] first entry and length of a node's segment
+  int* level;             // [T, 4] first node and nodes of the current level, nodes of the tree
+  int* lcounts;           // [T, lvl_cap, K] class counts of the left child of a level's split nodes
+  int64_t ldr;
+  int T, cap, lvl_cap, max_depth, min_leaf, m_feat, hist_bytes;
+  uint64_t seed;
+};
+void launch_tree_grow(const TreeGrowArgs& a, hipStream_t stream);
+struct TreePredictArgs {
+  TreeTable t;            // the held-out rows (cw: the training table's)
+  const int* feature;
+  const int* bin;
+  const int* left;
+  const int* counts;
+  int T, cap, soft;
+  int* conf;              // [K, K]
+};
+void launch_tree_predict(const TreePredictArgs& a, hipStream_t stream);
+// out[0..5] = f1, acc, real[0], real[1], real[0] - f1, real[1] - acc
+void launch_tree_scores(const int* conf, int K, const double* real, double* out, hipStream_t stream);
+
 struct GenWeightJob {
   const float* w;   // fp32 weight, element (n, k) at w[n * ldw + k * skw] (skw = 1: [N, K] rows; ldw = 1: input-major storage)
   int N, ldw, skw, kd, C;

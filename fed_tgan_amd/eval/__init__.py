@@ -1,3 +1,4 @@
 from .correlation import CorrelationScores, DeviceCorrelation  # noqa: F401
 from .privacy import DevicePrivacy, PrivacyScores  # noqa: F401
 from .utility_device import DeviceUtility, UtilityScores  # noqa: F401
+from .forest_device import DeviceForest, ForestScores  # noqa: F401

@@ -3,7 +3,8 @@ same classifier trained on the real training rows.
 
 Avg_JSD / Avg_WD, DCR / NNDR and Diff. Corr. compare the tables; this evaluator asks whether a model fitted on the
 generated rows classifies held-out real rows.  The classifier is a class-balanced, L2-regularised multinomial logistic
-regression only; the reference's decision tree, random forest and MLP stay with ``eval/utility.py`` (sklearn on a CSV).
+regression; the reference's decision tree and random forest are ``eval/forest_device.py``, its MLP stays with
+``eval/utility.py`` (sklearn on a CSV).
 Rows live in the space of the decoded table (``generate_decoded``'s ``[n, n_cols]`` float64: label codes in the
 categorical columns, log1p values in the ``non_negative_cols``); the real tables are brought there with
 :func:`fed_tgan_amd.eval.privacy.code_real_table`.

@@ -62,6 +62,7 @@ class LoadedGenerator:
     _privacy: dict = dataclasses.field(default_factory=dict, repr=False)      # the same for privacy()
     _correlation: dict = dataclasses.field(default_factory=dict, repr=False)  # and for correlation()
     _utility: dict = dataclasses.field(default_factory=dict, repr=False)      # and for utility()
+    _forest: dict = dataclasses.field(default_factory=dict, repr=False)       # and for tree_utility()
 
     def sample(self, n: int, where=None, max_passes: int = 64) -> np.ndarray:
         """[n, n_columns] decoded values (label codes for categoricals), float64.  A GPU table comes
@@ -116,20 +117,33 @@ class LoadedGenerator:
                                   where=where, max_passes=max_passes)[:2]
 
     def write_csv_all(self, path: str, n: int, score_real=None, privacy_real=None, corr_real=None, threads: int = 0,
-                      where=None, max_passes: int = 64, utility_real=None, utility_test=None, utility_iters: int = 200):
+                      where=None, max_passes: int = 64, utility_real=None, utility_test=None, utility_iters: int = 200,
+                      utility_models=("lr",), utility_trees: int = 100, utility_depth: int = 12):
         """:meth:`write_csv` with whichever of :meth:`score` (score_real), :meth:`privacy` (privacy_real),
         :meth:`correlation` (corr_real) and :meth:`utility` (utility_real, utility_test) are asked for, all of the
-        rows the CSV holds and all taken on the device before the copy.  Returns ((Avg_JSD, Avg_WD) | None, privacy
-        dict | None, correlation dict | None, utility dict | None)."""
+        rows the CSV holds and all taken on the device before the copy.  utility_models: ``"lr"`` (:meth:`utility`)
+        and / or ``"dt"`` / ``"rf"`` (:meth:`tree_utility`, with utility_trees and utility_depth), whose keys share
+        the utility dict.  Returns ((Avg_JSD, Avg_WD) | None, privacy dict | None, correlation dict | None, utility
+        dict | None)."""
+        utility_models = tuple(utility_models)
+        if not utility_models or set(utility_models) - {"lr", "dt", "rf"}:
+            raise ValueError(f"utility_models must be a non-empty subset of ('lr', 'dt', 'rf'), got {utility_models}")
         vals = self.device_table(n, where=where, max_passes=max_passes)
         sim = self._evaluator(score_real, n).score(vals) if score_real is not None else None
         priv = self._privacy_evaluator(privacy_real, n).score(vals) if privacy_real is not None else None
         corr = self._correlation_evaluator(corr_real, n).score(vals) if corr_real is not None else None
-        util = None
-        if utility_real is not None:
+        util = forest = None
+        if utility_real is not None and "lr" in utility_models:
             util = self._utility_evaluator(utility_real, utility_test, n, utility_iters).score(vals)
+        tree_models = tuple(m for m in ("dt", "rf") if m in utility_models)
+        if utility_real is not None and tree_models:
+            forest = self._forest_evaluator(utility_real, utility_test, n, utility_trees, utility_depth, 0,
+                                            tree_models).score(vals)
         self._write_values(path, self._to_host(vals), threads)
-        return tuple(s.floats() if s is not None else None for s in (sim, priv, corr, util))
+        out = [s.floats() if s is not None else None for s in (sim, priv, corr, util)]
+        if forest is not None:
+            out[3] = dict(out[3] or {}, **forest.floats())
+        return tuple(out)
 
     def utility(self, train_real, test_real=None, n: int = 40000, where=None, max_passes: int = 64,
                 iters: int = 200) -> dict:
@@ -157,6 +171,35 @@ class LoadedGenerator:
             self._utility[key] = (frames, DeviceUtility(train, test, self.meta, self.vocabs, self.engine.device,
                                                         ops=self.engine.ops, iters=int(iters), max_rows=int(n)))
         return self._utility[key][1]
+
+    def tree_utility(self, train_real, test_real=None, n: int = 40000, where=None, trees: int = 100,
+                     max_depth: int = 12, seed: int = 0, max_passes: int = 64) -> dict:
+        """Tree utility of n generated rows (eval/forest_device.py): a histogram decision tree and a random forest of
+        ``trees`` trees, both of depth ``max_depth`` at most and with balanced class weights, are fitted on them on
+        the engine's device and tested on real rows; ``dt_*`` / ``rf_*`` ``f1_fake`` / ``acc_fake`` against ``f1_real``
+        / ``acc_real`` of the same fits on ``train_real``, and their gaps.  Tables and the held-out default as for
+        :meth:`utility`.  The evaluator is kept per tables, n, trees, max_depth and seed."""
+        return self._forest_evaluator(train_real, test_real, n, trees, max_depth, seed).score(
+            self.device_table(n, where=where, max_passes=max_passes)).floats()
+
+    def _forest_evaluator(self, train_real, test_real, n: int, trees: int = 100, max_depth: int = 12, seed: int = 0,
+                          models=("dt", "rf")):
+        import pandas as pd
+        from ..eval.forest_device import DeviceForest
+        key = tuple(t if isinstance(t, str) or t is None else id(t) for t in (train_real, test_real)) + (
+            int(n), int(trees), int(max_depth), int(seed), tuple(models))
+        if key not in self._forest:
+            train = pd.read_csv(train_real) if isinstance(train_real, str) else train_real
+            test = pd.read_csv(test_real) if isinstance(test_real, str) else test_real
+            frames = (train, test)
+            if test is None:
+                held = np.arange(len(train)) % 5 == 4
+                train, test = train[~held].reset_index(drop=True), train[held].reset_index(drop=True)
+            self._forest.clear()
+            self._forest[key] = (frames, DeviceForest(train, test, self.meta, self.vocabs, self.engine.device,
+                                                      ops=self.engine.ops, trees=int(trees), max_depth=int(max_depth),
+                                                      seed=int(seed), max_rows=int(n), models=tuple(models)))
+        return self._forest[key][1]
 
     def correlation(self, real, n: int = 40000, where=None, max_passes: int = 64) -> dict:
         """Diff. Corr. of n generated rows against ``real`` (a DataFrame or a CSV path): generated and scored on the

@@ -739,3 +739,33 @@ class HipOps:
     def util_predict(self, tab, n, train_counts, W, conf, G, loss, real, out):
         """Same contract as TorchOps.util_predict."""
         self.L.util_predict(*self._util_table(tab, n), train_counts, W, conf, G, loss, real, out)
+
+    # ------------------------------------------------------------------ tree-utility evaluator (kernels/forest.hip)
+    TREE_CONT, TREE_CAT, TREE_TARGET = 0, 1, 2
+    TREE_MAX_BINS = 256          # kernels/launch.h: a bin is one byte
+    TREE_MAX_CLASSES = 64        # K: a lane per class
+    TREE_MAX_DEPTH = 20
+    TREE_MAX_FEATURES = 1024     # a node's per-feature candidates in LDS
+
+    def tree_pack(self, values, kind, slot, tab):
+        """Same contract as TorchOps.tree_pack."""
+        self.L.tree_pack(values, kind, slot, tab.card, tab.edges, tab.eoff, tab.bins, tab.y, tab.counts, tab.cw)
+
+    def tree_bootstrap(self, mult, n, bootstrap, seed):
+        """Same contract as TorchOps.tree_bootstrap."""
+        self.L.tree_bootstrap(mult, int(n), bool(bootstrap), int(seed))
+
+    def tree_grow(self, tab, n, model, max_depth, min_leaf, m_feat, seed):
+        """Same contract as TorchOps.tree_grow; model.rows / seg / level / lcounts are its scratch."""
+        self.L.tree_grow(tab.bins, tab.y, tab.counts, tab.cw, tab.nbins, int(tab.max_bins), int(n), model.mult,
+                         model.rows, model.feature, model.bin, model.left, model.heap, model.counts, model.seg,
+                         model.level, model.lcounts, int(max_depth), int(min_leaf), int(m_feat), int(seed))
+
+    def tree_predict(self, tab, n, cw, model, soft, conf):
+        """Same contract as TorchOps.tree_predict."""
+        self.L.tree_predict(tab.bins, tab.y, tab.counts, cw, int(n), model.feature, model.bin, model.left,
+                            model.counts, bool(soft), conf)
+
+    def tree_scores(self, conf, real, out):
+        """Same contract as TorchOps.tree_scores."""
+        self.L.tree_scores(conf, real, out)

@@ -25,7 +25,8 @@ CHECK_NAMES = {0: "sampler CSR pick outside the row lists", 1: "sampler data row
                4: "decode mode index >= K", 5: "one-hot gather index outside the conditional block",
                6: "encode label outside the lookup table",
                7: "conditional request index outside its tables",
-               8: "similarity evaluator: categorical code outside its vocabulary"}
+               8: "similarity evaluator: categorical code outside its vocabulary",
+               9: "tree evaluator: bin, class, row or node index outside its table"}
 
 _lock = threading.Lock()
 _loaded = None

@@ -895,3 +895,221 @@ class TorchOps:
         acc = torch.where(total > 0, tp.sum() / safe, torch.zeros_like(total))
         out[0], out[1], out[2], out[3] = f1, acc, real[0], real[1]
         out[4], out[5], out[6], out[7] = real[0] - f1, real[1] - acc, loss[0], G.abs().max()
+
+    # ------------------------------------------------------------------ tree-utility evaluator (eval/forest_device.py)
+    TREE_CONT, TREE_CAT, TREE_TARGET = 0, 1, 2
+    TREE_MAX_BINS, TREE_MAX_CLASSES, TREE_MAX_DEPTH, TREE_MAX_FEATURES = 256, 64, 20, 1024   # the HIP kernels' limits
+    TREE_STREAM_DRAW, TREE_STREAM_FEAT = 0x74726231, 0x74726632      # Philox stream ids no other call site uses
+
+    @staticmethod
+    def _tree_mulhilo(a: int, c):
+        """(hi, lo) 32-bit halves of a * c for a < 2^32 and int64 c < 2^32, without leaving 63 bits"""
+        lo16, hi16 = a * (c & 0xFFFF), a * (c >> 16)
+        t = hi16 + (lo16 >> 16)
+        return t >> 16, ((t & 0xFFFF) << 16) | (lo16 & 0xFFFF)
+
+    @classmethod
+    def tree_word(cls, seed: int, stream: int, w, hi, lo):
+        """first word of Philox4x32-10 (kernels/common.h) of the counter (lo, hi, stream, w) under the key seed, in
+        int64 tensors"""
+        c0, c1, c3 = (x if torch.is_tensor(x) else torch.tensor(int(x), dtype=torch.int64) for x in (lo, hi, w))
+        c0, c1, c3 = torch.broadcast_tensors(c0.long(), c1.long().to(c0.device), c3.long().to(c0.device))
+        c2 = torch.full_like(c0, int(stream))
+        k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+        for _ in range(10):
+            h0, l0 = cls._tree_mulhilo(0xD2511F53, c0)
+            h1, l1 = cls._tree_mulhilo(0xCD9E8D57, c2)
+            c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
+            k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+        return c0
+
+    def tree_pack(self, values, kind, slot, tab):
+        """Bins the row-major float64 table ``values`` [n, n_cols] into ``tab`` (eval.forest_device.TreeTable):
+        tab.bins[f, r] (uint8) is, for a continuous feature, the number of its edges below the value (0 for a NaN)
+        and, for a categorical one with K_c categories, the code or K_c where the value is no code; tab.y the target's
+        code or K; tab.counts the valid rows per class and tab.cw the balanced class weights ``n_valid / (K_present
+        count_c)``, 0 for an absent class."""
+        n, K = int(values.shape[0]), tab.K
+        eoff = tab.eoff.tolist()
+        card = tab.card.tolist()
+        for j, (k, f) in enumerate(zip(kind.tolist(), slot.tolist())):
+            v = values[:, j]
+            if k == self.TREE_CONT:
+                e = tab.edges[eoff[f]:eoff[f + 1]]
+                b = torch.searchsorted(e, torch.nan_to_num(v, nan=float("-inf")).contiguous(), right=False)
+                tab.bins[f, :n] = b.clamp(max=self.TREE_MAX_BINS - 1).to(torch.uint8)
+                continue
+            Kc = K if k == self.TREE_TARGET else card[f]
+            ok = (v >= 0) & (v < Kc)
+            code = torch.where(ok, torch.where(ok, v, torch.zeros_like(v)).long(), torch.full_like(v, Kc, dtype=torch.int64))
+            if k == self.TREE_TARGET:
+                tab.y[:n] = code.to(torch.int32)
+                tab.counts.copy_(torch.bincount(code[ok], minlength=K)[:K].to(torch.int32))
+            else:
+                tab.bins[f, :n] = code.to(torch.uint8)
+        cnt = tab.counts.to(torch.float64)
+        nv, present = tab.counts.sum().to(torch.float64), (tab.counts > 0).sum().to(torch.float64)
+        tab.cw.copy_(torch.where(cnt > 0, nv / (present * torch.where(cnt > 0, cnt, torch.ones_like(cnt))),
+                                 torch.zeros_like(cnt)))
+
+    def tree_bootstrap(self, mult, n, bootstrap, seed):
+        """mult [T, >= n] int32: 1 per row, or with ``bootstrap`` how often tree t drew the row among its n draws,
+        draw j being row ``mulhi32(word(t, j), n)``."""
+        T = int(mult.shape[0])
+        if not bootstrap:
+            mult[:, :n] = 1
+            return
+        dev = mult.device
+        j = torch.arange(n, dtype=torch.int64, device=dev)[None, :]
+        t = torch.arange(T, dtype=torch.int64, device=dev)[:, None]
+        w = self.tree_word(seed, self.TREE_STREAM_DRAW, 0, t, j)
+        hi, _ = self._tree_mulhilo(int(n), w)
+        m = torch.zeros(T, n, dtype=torch.int64, device=dev)
+        m.scatter_add_(1, hi, torch.ones_like(hi))
+        mult[:, :n] = m.to(torch.int32)
+
+    def tree_grow(self, tab, n, model, max_depth, min_leaf, m_feat, seed):
+        """Grows the ``model.T`` trees of ``model`` (eval.forest_device.TreeModel) level by level on the first n rows
+        of ``tab`` with the multiplicities model.mult (rows with multiplicity 0 or no valid class are left out); the
+        criterion, the tie order, the competing features and the node layout are those of eval/forest_device.py."""
+        dev = tab.bins.device
+        K, F, NB = tab.K, tab.F, int(tab.max_bins)
+        bins, y, w = tab.bins[:, :n].long(), tab.y[:n].long(), tab.cw
+        nb = tab.nbins.long()
+        m_feat = min(int(m_feat), F)
+        model.feature.fill_(-1)
+        for z in (model.bin, model.left, model.heap, model.counts):
+            z.zero_()
+        ar_b = torch.arange(NB, device=dev)
+        ar_f = torch.arange(F, device=dev)
+        chunk = max(1, (1 << 22) // (F * NB * K))
+        for t in range(model.T):
+            mult = model.mult[t, :n].long()
+            rows = ((mult > 0) & (y >= 0) & (y < K)).nonzero().flatten()
+            yr, mr, br = y[rows], mult[rows], bins[:, rows]
+            item = torch.zeros_like(rows)
+            model.heap[t, 0] = 1
+            model.counts[t, 0] = torch.zeros(K, dtype=torch.int64, device=dev).index_add_(0, yr, mr).to(torch.int32)
+            start, count = 0, 1
+            for _ in range(int(max_depth)):
+                tot = model.counts[t, start:start + count].long()
+                heap = model.heap[t, start:start + count].long()
+                cand = (tot > 0).sum(dim=1) > 1
+                bf = torch.full((count,), -1, dtype=torch.int64, device=dev)
+                bb = torch.zeros(count, dtype=torch.int64, device=dev)
+                lc = torch.zeros(count, K, dtype=torch.int64, device=dev)
+                for i0 in range(0, count, chunk):
+                    i1 = min(count, i0 + chunk)
+                    if not bool(cand[i0:i1].any()):
+                        continue
+                    I = i1 - i0
+                    idx = ((item >= i0) & (item < i1)).nonzero().flatten()
+                    flat = (((item[idx] - i0)[None, :] * F + ar_f[:, None]) * NB + br[:, idx]) * K + yr[idx][None, :]
+                    hist = torch.zeros(I * F * NB * K, dtype=torch.int64, device=dev)
+                    hist.index_add_(0, flat.flatten(), mr[idx][None, :].expand(F, -1).flatten())
+                    pre = hist.view(I, F, NB, K).cumsum(dim=2)
+                    totc = tot[i0:i1]
+                    nl = pre.sum(dim=3)
+                    nr = totc.sum(dim=1)[:, None, None] - nl
+                    TL = torch.zeros(I, F, NB, dtype=torch.float64, device=dev)
+                    QL, TR, QR = TL.clone(), TL.clone(), TL.clone()
+                    for c in range(K):
+                        ml = pre[..., c].to(torch.float64) * w[c]
+                        mrr = (totc[:, c][:, None, None] - pre[..., c]).to(torch.float64) * w[c]
+                        TL = TL + ml
+                        QL = QL + ml * ml
+                        TR = TR + mrr
+                        QR = QR + mrr * mrr
+                    valid = ((nl >= min_leaf) & (nr >= min_leaf) & (TL > 0) & (TR > 0) &
+                             (ar_b[None, None, :] < (nb - 1)[None, :, None]) & cand[i0:i1][:, None, None])
+                    one = torch.ones_like(TL)
+                    score = torch.where(valid, QL / torch.where(valid, TL, one) + QR / torch.where(valid, TR, one), -one)
+                    fs = score.max(dim=2).values
+                    fb = torch.where((score == fs[..., None]) & valid, ar_b, NB).min(dim=2).values
+                    comp = valid.any(dim=2)
+                    if m_feat < F:
+                        keys = self.tree_word(seed, self.TREE_STREAM_FEAT, heap[i0:i1][:, None], t, ar_f[None, :])
+                        order = torch.where(comp, (keys << 10) | ar_f[None, :], torch.full_like(keys, 1 << 62))
+                        rank = torch.empty_like(order)
+                        rank.scatter_(1, order.argsort(dim=1), ar_f[None, :].expand(I, -1).contiguous())
+                        comp = comp & (rank < m_feat)
+                    fs = torch.where(comp, fs, -torch.ones_like(fs))
+                    best = fs.max(dim=1).values
+                    f_star = torch.where((fs == best[:, None]) & comp, ar_f, F).min(dim=1).values
+                    has = f_star < F
+                    f_c = f_star.clamp(max=F - 1)
+                    b_star = fb.gather(1, f_c[:, None])[:, 0].clamp(max=NB - 1)
+                    bf[i0:i1] = torch.where(has, f_star, -torch.ones_like(f_star))
+                    bb[i0:i1] = torch.where(has, b_star, torch.zeros_like(b_star))
+                    lc[i0:i1] = pre[torch.arange(I, device=dev), f_c, b_star]
+                split = bf >= 0
+                rank = split.long().cumsum(0) - 1
+                nxt = start + count
+                n_split = int(split.sum())
+                model.feature[t, start:nxt] = bf.to(torch.int32)
+                model.bin[t, start:nxt] = bb.to(torch.int32)
+                if n_split == 0:
+                    break
+                l = (nxt + 2 * rank)[split]
+                model.left[t, start:nxt] = torch.where(split, nxt + 2 * rank, torch.zeros_like(rank)).to(torch.int32)
+                model.heap[t, l] = (2 * heap[split]).to(torch.int32)
+                model.heap[t, l + 1] = (2 * heap[split] + 1).to(torch.int32)
+                model.counts[t, l] = lc[split].to(torch.int32)
+                model.counts[t, l + 1] = (tot[split] - lc[split]).to(torch.int32)
+                go = split[item]
+                right = br[bf[item].clamp(min=0), torch.arange(item.numel(), device=dev)] > bb[item]
+                new_item = 2 * rank[item] + right.long()
+                item, yr, mr, br = new_item[go], yr[go], mr[go], br[:, go]
+                start, count = nxt, 2 * n_split
+
+    def tree_predict(self, tab, n, cw, model, soft, conf):
+        """conf [K, K] int32: the first n rows of ``tab`` by (target code, predicted class).  A row walks every tree
+        by its bins to a leaf with masses ``m_c = n_c cw_c``; hard (one tree): the largest m_c; soft: the largest sum
+        over the trees, in tree order, of ``m_c / T_leaf`` (T_leaf the sum of m_c in class order; a leaf with T_leaf =
+        0 adds nothing).  The lowest class wins a tie; rows whose target is no code are skipped."""
+        dev = tab.bins.device
+        K = tab.K
+        bins, y = tab.bins[:, :n].long(), tab.y[:n].long()
+        ar = torch.arange(n, device=dev)
+        P = torch.zeros(n, K, dtype=torch.float64, device=dev)
+        for t in range(model.T):
+            feature, bn, left = model.feature[t].long(), model.bin[t].long(), model.left[t].long()
+            node = torch.zeros(n, dtype=torch.int64, device=dev)
+            for _ in range(self.TREE_MAX_DEPTH + 1):
+                f = feature[node]
+                act = f >= 0
+                if not bool(act.any()):
+                    break
+                b = bins[f.clamp(min=0), ar]
+                node = torch.where(act, left[node] + (b > bn[node]).long(), node)
+            m = model.counts[t].long()[node].to(torch.float64) * cw[None, :]
+            if not soft:
+                P = m
+                break
+            T = torch.zeros(n, dtype=torch.float64, device=dev)
+            for c in range(K):
+                T = T + m[:, c]
+            ok = (T > 0)[:, None]
+            P = P + torch.where(ok, m / torch.where(ok, T[:, None], torch.ones_like(m)), torch.zeros_like(m))
+        idx = torch.arange(K, device=dev)[None, :].expand_as(P)
+        pred = torch.where(P == P.max(dim=1).values[:, None], idx, torch.full_like(idx, K)).min(dim=1).values
+        pred = pred.clamp(max=K - 1)
+        ok = (y >= 0) & (y < K)
+        conf.copy_(torch.bincount(y[ok] * K + pred[ok], minlength=K * K).view(K, K).to(conf.dtype))
+
+    def tree_scores(self, conf, real, out):
+        """out[0..5] = weighted F1, accuracy, real[0], real[1], real[0] - F1, real[1] - accuracy of the confusion
+        matrix, the F1 terms added in class order"""
+        cd = conf.to(torch.float64)
+        rs, cs, tp = cd.sum(dim=1), cd.sum(dim=0), torch.diagonal(cd)
+        den = rs + cs
+        f = torch.where(den > 0, (2.0 * tp) / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(den))
+        total = rs.sum()
+        safe = torch.where(total > 0, total, torch.ones_like(total))
+        acc_f1 = torch.zeros((), dtype=torch.float64, device=conf.device)
+        for c in range(int(conf.shape[0])):
+            acc_f1 = acc_f1 + rs[c] * f[c]
+        f1 = torch.where(total > 0, acc_f1 / safe, torch.zeros_like(total))
+        acc = torch.where(total > 0, tp.sum() / safe, torch.zeros_like(total))
+        out[0], out[1], out[2], out[3] = f1, acc, real[0], real[1]
+        out[4], out[5] = real[0] - f1, real[1] - acc
