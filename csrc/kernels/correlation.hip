@@ -17,6 +17,7 @@
 // Integer adds commute and every fp64 sum has an order fixed by the shapes alone, so a table scores bit-identically
 // on every run.  Codes are clamped before they index anything.
 #include "common.h"
+#include "eval_common.h"
 #include "launch.h"
 
 #include <math.h>
@@ -26,8 +27,6 @@ namespace fedtgan {
 
 constexpr int CORR_THREADS = 256;
 constexpr int CORR_WAVES = CORR_THREADS / WAVE;
-
-__device__ __forceinline__ int corr_clamp(int code, int K) { return code < 0 ? K : (code > K ? K : code); }
 
 int64_t g_corr_part_target = CORR_PART_TARGET;
 
@@ -73,8 +72,7 @@ __global__ __launch_bounds__(CORR_THREADS) void corr_pack_kernel(CorrPackArgs a)
   const double v = a.values[i];
   if (k == CORR_CAT) {
     if (s >= 0 && s < a.n_cat) {
-      const int K = a.card[s];
-      a.cat_t[(size_t)s * a.ldk + r] = (v >= 0.0 && v < (double)K) ? (int)v : K;     // (NaN fails both comparisons)
+      a.cat_t[(size_t)s * a.ldk + r] = code_or_overflow(v, a.card[s]);
     }
   } else if (s >= 0 && s < a.n_cont) {
     a.cont[r * a.n_cont + s] = v;
@@ -184,7 +182,7 @@ __global__ __launch_bounds__(CORR_THREADS) void corr_moments_kernel(CorrMomentsA
 #pragma unroll
     for (int t = 0; t < 2; ++t)
       if (live && hcol[t] >= 0)
-        x[t] = corr_clamp(a.cat_t[(size_t)hcol[t] * a.ldk + row], hcard[t]) == hbin[t] ? 1.0 : 0.0;
+        x[t] = code_clamp(a.cat_t[(size_t)hcol[t] * a.ldk + row], hcard[t]) == hbin[t] ? 1.0 : 0.0;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -255,8 +253,8 @@ __global__ __launch_bounds__(CORR_THREADS) void corr_counts_kernel(CorrCountsArg
     for (int i = tid; i < nb; i += CORR_THREADS) hist[i] = 0;
     __syncthreads();
     for (int r = r0 + tid; r < r1; r += CORR_THREADS) {
-      const int x = corr_clamp(pa[r], ka - 1);
-      const int y = pb ? corr_clamp(pb[r], kb - 1) : 0;
+      const int x = code_clamp(pa[r], ka - 1);
+      const int y = pb ? code_clamp(pb[r], kb - 1) : 0;
       atomicAdd(&hist[x * kb + y], 1);
     }
     __syncthreads();
@@ -266,8 +264,8 @@ __global__ __launch_bounds__(CORR_THREADS) void corr_counts_kernel(CorrCountsArg
     }
   } else {
     for (int r = r0 + tid; r < r1; r += CORR_THREADS) {
-      const int x = corr_clamp(pa[r], ka - 1);
-      const int y = pb ? corr_clamp(pb[r], kb - 1) : 0;
+      const int x = code_clamp(pa[r], ka - 1);
+      const int y = pb ? code_clamp(pb[r], kb - 1) : 0;
       atomicAdd(&table[(long long)x * kb + y], 1);
     }
   }

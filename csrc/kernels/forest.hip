@@ -34,6 +34,8 @@
 
 #pragma clang fp contract(off)
 
+#include "eval_common.h"      // below the pragma: its inline functions compile without contraction here
+
 namespace fedtgan {
 
 constexpr int TREE_THREADS = 256;
@@ -82,17 +84,15 @@ __global__ __launch_bounds__(TREE_THREADS) void tree_pack_kernel(TreePackArgs a)
   const int k = a.kind[c], f = a.slot[c];
   const double v = a.values[i];
   if (k == TREE_TARGET) {
-    const bool ok = v >= 0.0 && v < (double)t.K;          // (NaN fails both comparisons)
-    const int code = ok ? (int)v : t.K;
+    const int code = code_or_overflow(v, t.K);
     t.y[r] = code;
-    if (ok) atomicAdd(&t.counts[code], 1);
+    if (is_code(v, t.K)) atomicAdd(&t.counts[code], 1);
     return;
   }
   if (f < 0 || f >= t.F) return;
   int b;
   if (k == TREE_CAT) {
-    const int K = a.card[f];
-    b = (v >= 0.0 && v < (double)K) ? (int)v : K;
+    b = code_or_overflow(v, a.card[f]);
   } else {                                                  // the number of edges below v; a NaN is above none
     const int e0 = tree_clampi(a.eoff[f], 0, a.n_edges), e1 = tree_clampi(a.eoff[f + 1], e0, a.n_edges);
     int lo = e0, hi = e1;
@@ -109,20 +109,9 @@ __global__ __launch_bounds__(TREE_THREADS) void tree_pack_kernel(TreePackArgs a)
 __global__ __launch_bounds__(WAVE) void tree_weights_kernel(TreeTable t) {
   __shared__ int head[2];
   const int tid = threadIdx.x;
-  if (tid == 0) {
-    int nv = 0, present = 0;
-    for (int c = 0; c < t.K; ++c) {
-      nv += t.counts[c];
-      present += t.counts[c] > 0;
-    }
-    head[0] = nv;
-    head[1] = present;
-  }
+  if (tid == 0) class_head(t.counts, t.K, head[0], head[1]);
   __syncthreads();
-  if (tid < t.K) {
-    const int cnt = t.counts[tid];
-    t.cw[tid] = cnt > 0 ? (double)head[0] / ((double)head[1] * (double)cnt) : 0.0;
-  }
+  if (tid < t.K) t.cw[tid] = balanced_weight(head[0], head[1], t.counts[tid]);
 }
 
 void launch_tree_pack(const TreePackArgs& a, hipStream_t stream) {
@@ -599,24 +588,7 @@ __global__ __launch_bounds__(WAVE) void tree_scores_kernel(const int* conf, int 
     tp[tid] = conf[tid * K + tid];
   }
   __syncthreads();
-  if (tid == 0) {
-    long long total = 0, right = 0;
-    double f1 = 0.0;
-    for (int c = 0; c < K; ++c) {
-      total += rs[c];
-      right += tp[c];
-      const int den = rs[c] + cs[c];            // 2 tp + fp + fn
-      if (den > 0) f1 = f1 + (double)rs[c] * ((2.0 * (double)tp[c]) / (double)den);
-    }
-    f1 = total > 0 ? f1 / (double)total : 0.0;
-    const double acc = total > 0 ? (double)right / (double)total : 0.0;
-    out[0] = f1;
-    out[1] = acc;
-    out[2] = real[0];
-    out[3] = real[1];
-    out[4] = real[0] - f1;
-    out[5] = real[1] - acc;
-  }
+  if (tid == 0) confusion_scores(rs, cs, tp, K, real, out);
 }
 
 void launch_tree_scores(const int* conf, int K, const double* real, double* out, hipStream_t stream) {

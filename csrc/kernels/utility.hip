@@ -21,6 +21,7 @@
 // Integer adds commute and every fp64 sum has an order fixed by the shapes alone, so a table scores bit-identically on
 // every run.  Codes are clamped before they index anything.  An iteration is ordinary launches on one stream.
 #include "common.h"
+#include "eval_common.h"
 #include "launch.h"
 
 #include <math.h>
@@ -39,8 +40,6 @@ typedef double util_d4 __attribute__((ext_vector_type(4)));
 static_assert(UTIL_MAX_FEATURES <= UTIL_FACTOR_THREADS, "a lane of util_factor_kernel owns one column");
 static_assert(UTIL_ROWS == 64 && UTIL_THREADS == 256 && UTIL_SLAB == 16 * 4 * UTIL_WAVES, "util_grad_kernel's tiling");
 static_assert(UTIL_CHUNK % UTIL_ROWS == 0 && UTIL_MAX_CLASSES == 64, "row blocks; one lane per class");
-
-__device__ __forceinline__ int util_clamp(int code, int K) { return code < 0 ? K : (code > K ? K : code); }
 
 static int64_t util_chunks(int64_t n) {
   const int64_t chunks = (n + UTIL_CHUNK - 1) / UTIL_CHUNK;
@@ -109,7 +108,7 @@ __device__ __forceinline__ UFeat util_feat(const UtilTable& t, int f) {
 // (row < t.n is the caller's)
 __device__ __forceinline__ double util_fval(const UtilTable& t, const UFeat& d, int row) {
   if (d.kind == 1) return t.cont[(size_t)row * t.n_cont + d.col];
-  if (d.kind == 2) return util_clamp(t.cat_t[(size_t)d.col * t.ldk + row], d.card) == d.bin ? 1.0 : 0.0;
+  if (d.kind == 2) return code_clamp(t.cat_t[(size_t)d.col * t.ldk + row], d.card) == d.bin ? 1.0 : 0.0;
   return d.kind == 3 ? 1.0 : 0.0;
 }
 
@@ -128,15 +127,11 @@ __global__ __launch_bounds__(UTIL_THREADS) void util_pack_kernel(UtilPackArgs a)
   const int k = a.kind[c], s = a.slot[c];
   const double v = a.values[i];
   if (k == UTIL_TARGET) {
-    const bool ok = v >= 0.0 && v < (double)t.K;          // (NaN fails both comparisons)
-    const int code = ok ? (int)v : t.K;
+    const int code = code_or_overflow(v, t.K);
     t.y[r] = code;
-    if (ok) atomicAdd(&t.counts[code], 1);
+    if (is_code(v, t.K)) atomicAdd(&t.counts[code], 1);
   } else if (k == UTIL_CAT) {
-    if (s >= 0 && s < t.n_cat) {
-      const int K = t.card[s];
-      t.cat_t[(size_t)s * t.ldk + r] = (v >= 0.0 && v < (double)K) ? (int)v : K;
-    }
+    if (s >= 0 && s < t.n_cat) t.cat_t[(size_t)s * t.ldk + r] = code_or_overflow(v, t.card[s]);
   } else if (s >= 0 && s < t.n_cont) {
     t.cont[r * t.n_cont + s] = (v - a.mean[s]) / a.sd[s];
   }
@@ -146,20 +141,9 @@ __global__ __launch_bounds__(UTIL_THREADS) void util_weights_kernel(UtilTable t)
   __shared__ double cw[UTIL_MAX_CLASSES];
   __shared__ int head[2];
   const int tid = threadIdx.x;
-  if (tid == 0) {
-    int nv = 0, present = 0;
-    for (int c = 0; c < t.K; ++c) {
-      nv += t.counts[c];
-      present += t.counts[c] > 0;
-    }
-    head[0] = nv;
-    head[1] = present;
-  }
+  if (tid == 0) class_head(t.counts, t.K, head[0], head[1]);
   __syncthreads();
-  if (tid < t.K) {
-    const int cnt = t.counts[tid];
-    cw[tid] = cnt > 0 ? (double)head[0] / ((double)head[1] * (double)cnt) : 0.0;
-  }
+  if (tid < t.K) cw[tid] = balanced_weight(head[0], head[1], t.counts[tid]);
   __syncthreads();
   if (blockIdx.x == 0 && tid == 0) {
     double S = 0.0;
@@ -353,7 +337,7 @@ __device__ __forceinline__ void util_logits_row(const UtilTable& t, const double
 #pragma unroll
   for (int e = 0; e < CT * 4; ++e) z[e] = cq + 4 * e < K ? Z[zr][cq + 4 * e] : 0.0;
   for (int cc = 0; cc < t.n_cat; ++cc) {
-    const int f = nc + t.offs[cc] + util_clamp(t.cat_t[(size_t)cc * t.ldk + row], t.card[cc]);
+    const int f = nc + t.offs[cc] + code_clamp(t.cat_t[(size_t)cc * t.ldk + row], t.card[cc]);
     if (f >= nc && f < t.D - 1) {
       const double* base = P + (size_t)f * K;
 #pragma unroll
@@ -604,22 +588,7 @@ __global__ __launch_bounds__(UTIL_THREADS) void util_scores_kernel(const int* co
     __syncthreads();
   }
   if (tid == 0) {
-    long long total = 0, right = 0;
-    double f1 = 0.0;
-    for (int c = 0; c < K; ++c) {
-      total += rs[c];
-      right += tp[c];
-      const int den = rs[c] + cs[c];            // 2 tp + fp + fn
-      if (den > 0) f1 += (double)rs[c] * (2.0 * (double)tp[c] / (double)den);
-    }
-    f1 = total > 0 ? f1 / (double)total : 0.0;
-    const double acc = total > 0 ? (double)right / (double)total : 0.0;
-    out[0] = f1;
-    out[1] = acc;
-    out[2] = real[0];
-    out[3] = real[1];
-    out[4] = real[0] - f1;
-    out[5] = real[1] - acc;
+    confusion_scores(rs, cs, tp, K, real, out);
     out[6] = loss[0];
     out[7] = sm[0];
   }

@@ -33,16 +33,12 @@ first's oracle.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence
 
-import numpy as np
 import pandas as pd
 import torch
 
-from ..data.constants import CATEGORICAL
-from ..data.decode import meta_column_names
-from .device import GraphedPass
-from .privacy import code_real_table
+from .base import DeviceEvaluator, category_counts, coded_table, column_slots, most_categories
 
 CORR_CONT, CORR_CAT = 0, 1
 KEYS = ("corr_diff", "corr_mean_abs", "corr_max_abs", "corr_diff_rr")
@@ -84,63 +80,23 @@ class CorrelationScores:
         return frame.head(max(int(k), 0)).reset_index(drop=True)
 
 
-class DeviceCorrelation(GraphedPass):
+class DeviceCorrelation(DeviceEvaluator):
+    DATES = "the decoded table holds their parts, not the dates, so columns would not be comparable"
+
     def __init__(self, real, meta: dict, vocabs: Sequence, device, ops=None, max_rows: int = 40000,
                  baseline: bool = True, graph: bool = False, cardinalities: Optional[Sequence[int]] = None,
                  max_scratch_bytes: int = 256 << 20):
         """real: the real table as a DataFrame, or already coded as a float64 [m, n_cols] array.  cardinalities:
         categories per categorical column (in column order), for a coded array whose codes do not show them all."""
-        if meta.get("date_info"):
-            raise ValueError("DeviceCorrelation: the table has date columns; the decoded table holds their parts, "
-                             "not the dates, so columns would not be comparable")
-        self.device = torch.device(device)
-        if ops is None:
-            if self.device.type == "cuda":
-                from ..ops.hip import HipOps
-                ops = HipOps(self.device)
-            else:
-                from ..ops.ref import TorchOps
-                ops = TorchOps()
-        self.ops = ops
-        self.max_rows = int(max_rows)
-        if self.max_rows < 1:
-            raise ValueError("DeviceCorrelation: max_rows must be >= 1")
-        self.names: List[str] = meta_column_names(meta)
-        self.n_cols = len(self.names)
-        kind = [CORR_CAT if c["type"] == CATEGORICAL else CORR_CONT for c in meta["columns"]]
-        slot, n_cat, n_cont = [], 0, 0
-        for k in kind:
-            slot.append(n_cat if k == CORR_CAT else n_cont)
-            n_cat += k == CORR_CAT
-            n_cont += k == CORR_CONT
-        self.kinds, self.n_cat, self.n_cont = kind, n_cat, n_cont
-        if isinstance(real, pd.DataFrame):
-            coded = code_real_table(real, meta, vocabs)
-        else:
-            coded = np.ascontiguousarray(np.asarray(real, dtype=np.float64))
-            if coded.ndim != 2 or coded.shape[1] != self.n_cols:
-                raise ValueError(f"DeviceCorrelation: expected a coded [m, {self.n_cols}] real table, got "
-                                 f"{coded.shape}")
-        m = coded.shape[0]
-        if m < 1:
-            raise ValueError("DeviceCorrelation: the real table is empty")
-        for j, k in enumerate(kind):
-            col = coded[:, j]
-            if not np.isfinite(col).all() or (k == CORR_CAT and (col < 0).any()):
-                raise ValueError(f"DeviceCorrelation: the real column {self.names[j]!r} holds a value that is not a "
-                                 + ("category code" if k == CORR_CAT else "finite number"))
-        self.n_real = m
+        super().__init__(meta, device, ops, max_rows, graph)
+        ops = self.ops
+        self.kinds = kind = [CORR_CAT if cat else CORR_CONT for cat in self.is_cat]
+        slot, count = column_slots(kind)
+        self.n_cat, self.n_cont = n_cat, n_cont = count.get(CORR_CAT, 0), count.get(CORR_CONT, 0)
+        coded = coded_table(real, meta, vocabs, self.who)
+        self.n_real = m = coded.shape[0]
         cat_cols = [j for j, k in enumerate(kind) if k == CORR_CAT]
-        if cardinalities is not None and len(cardinalities) != n_cat:
-            raise ValueError(f"DeviceCorrelation: cardinalities needs one entry per categorical column ({n_cat})")
-        card = []
-        for s, j in enumerate(cat_cols):
-            K = 1 + int(coded[:, j].max())
-            if s < len(vocabs):
-                K = max(K, len(vocabs[s]))
-            if cardinalities is not None:
-                K = max(K, int(cardinalities[s]))
-            card.append(K)
+        card = category_counts(coded, cat_cols, vocabs, cardinalities, self.who)
         self.card_list = card
         offs = [0]
         for K in card:
@@ -158,11 +114,10 @@ class DeviceCorrelation(GraphedPass):
         self.global_pairs = [(a, b) for a, b, ka, kb in pairs if ka * kb > lds_limit]
         self.scratch_bytes = 4 * poff[-1]
         if self.scratch_bytes > int(max_scratch_bytes) or poff[-1] >= 2 ** 31 or self.W >= 2 ** 31:
-            worst = sorted(range(n_cat), key=lambda s: -card[s])[:5]
             raise ValueError(
                 f"DeviceCorrelation: the contingency tables need {self.scratch_bytes} bytes of scratch, more than "
-                f"max_scratch_bytes = {int(max_scratch_bytes)}; the columns with the most categories are "
-                + ", ".join(f"{self.names[cat_cols[s]]!r} ({card[s]})" for s in worst))
+                f"max_scratch_bytes = {int(max_scratch_bytes)}; "
+                + most_categories([self.names[j] for j in cat_cols], card))
         dev = self.device
         i32 = dict(dtype=torch.int32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
@@ -192,9 +147,6 @@ class DeviceCorrelation(GraphedPass):
         self.scores.zero_()
         self.scores[3] = rr
         self._alloc(self.max_rows)
-        self.graph = bool(graph) and dev.type == "cuda"
-        self._graphs: Dict[Tuple[int, int], object] = {}
-        self._staged = None
 
     def _alloc(self, rows: int) -> None:
         dev = self.device
@@ -214,21 +166,11 @@ class DeviceCorrelation(GraphedPass):
         self._matrix(values, n, self.A)
         self.ops.corr_diff(self.A_real, self.A, self.scores)
 
+    def _result(self, n: int) -> CorrelationScores:
+        return CorrelationScores(self.scores.clone(), self.A.clone(), self)
+
     def score(self, values: torch.Tensor) -> CorrelationScores:
         """values: [n, n_cols] float64 on the evaluator's device, as ``generate_decoded`` returns them (finite
         values in the continuous columns are a precondition).  The work is queued on the current stream; the
         returned scores are device tensors and nothing waits for them."""
-        if values.dim() != 2 or values.shape[1] != self.n_cols or values.dtype != torch.float64:
-            raise ValueError(f"score: expected a float64 [n, {self.n_cols}] table, got {tuple(values.shape)} "
-                             f"{values.dtype}")
-        if values.device != self.scores.device:
-            raise ValueError(f"score: the table is on {values.device}, the evaluator on {self.scores.device}")
-        n = int(values.shape[0])
-        if n < 1 or n > self.max_rows:
-            raise ValueError(f"score: {n} rows; this evaluator's buffers hold 1..{self.max_rows}")
-        values = values.contiguous()
-        if self.graph:
-            self._replay(values, n)
-        else:
-            self._launch(values, n)
-        return CorrelationScores(self.scores.clone(), self.A.clone(), self)
+        return super().score(values)

@@ -21,18 +21,17 @@ matrix does not hold, so the scores would not be comparable.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
 import torch
 
 from ..data.constants import CATEGORICAL, EMPTY
-from ..data.decode import meta_column_names
-from ..utils.devsync import warm_and_capture
+from .base import MAX_GRAPHS, GraphedPass  # noqa: F401  (re-exported: tests and tools import them from here)
+from .base import DeviceEvaluator, column_slots
 
 SIM_PLAIN, SIM_NONNEG, SIM_CAT = 0, 1, 2
-MAX_GRAPHS = 4     # captured passes that read the caller's own buffer; tables beyond them are staged into ours
 
 
 class SimilarityScores:
@@ -73,55 +72,20 @@ def _csv_string(s: str) -> str:
     return " " if s == EMPTY else s
 
 
-class GraphedPass:
-    """A fixed launch sequence ``_launch(values, n)`` over buffers allocated at construction, replayed as a hipGraph.
-    The evaluator provides ``device``, ``max_rows``, ``n_cols`` and sets ``_graphs = {}``, ``_staged = None``."""
+class DeviceSimilarity(DeviceEvaluator):
+    DATES = "the CSV re-joins their parts into one column, so device scores would not be comparable with stat_sim"
 
-    def _replay(self, values: torch.Tensor, n: int) -> None:
-        # a captured pass reads the buffer it was captured on: generate_decoded returns the same one per n, so the
-        # first few (n, buffer) pairs get a graph of their own; any further table is staged into one of ours
-        g = self._graphs.get((n, values.data_ptr()))
-        if g is None and len(self._graphs) >= MAX_GRAPHS:
-            if self._staged is None:
-                self._staged = torch.empty(self.max_rows, self.n_cols, dtype=torch.float64, device=self.device)
-            stage = self._staged[:n]
-            stage.copy_(values)
-            values = stage
-            g = self._graphs.get((n, values.data_ptr()))
-        key = (n, values.data_ptr())
-        if g is None:
-            def launch():
-                self._launch(values, n)
-            g, = warm_and_capture(self.device, launch, [launch])
-            self._graphs[key] = g
-        g.replay()
-
-
-class DeviceSimilarity(GraphedPass):
     def __init__(self, real: pd.DataFrame, meta: dict, vocabs: Sequence, device, ops=None, max_rows: int = 40000,
                  graph: bool = False):
-        if meta.get("date_info"):
-            raise ValueError("DeviceSimilarity: the table has date columns; the CSV re-joins their parts into one "
-                             "column, so device scores would not be comparable with stat_sim")
-        self.device = torch.device(device)
-        if ops is None:
-            if self.device.type == "cuda":
-                from ..ops.hip import HipOps
-                ops = HipOps(self.device)
-            else:
-                from ..ops.ref import TorchOps
-                ops = TorchOps()
-        self.ops = ops
-        self.max_rows = int(max_rows)
-        if self.max_rows < 1:
-            raise ValueError("DeviceSimilarity: max_rows must be >= 1")
-        names = meta_column_names(meta)
+        super().__init__(meta, device, ops, max_rows, graph)
+        ops, names = self.ops, self.names
         missing = [n for n in names if n not in real.columns]
         if missing:
             raise ValueError(f"DeviceSimilarity: the real table lacks columns {missing[:5]}")
         nonneg = set(meta.get("non_negative_cols") or [])
-        kind, slot, vocab_n, cat_counts, cont_vals = [], [], [], [], []
-        self.col_of: Dict[str, Tuple[int, int]] = {}
+        kind = [SIM_CAT if cat else SIM_NONNEG if name in nonneg else SIM_PLAIN for name, cat in zip(names, self.is_cat)]
+        slot, _ = column_slots(kind, {SIM_NONNEG: SIM_PLAIN})
+        vocab_n, cat_counts, cont_vals = [], [], []
         cursor = 0
         for c in meta["columns"]:
             name = c["column_name"]
@@ -138,18 +102,14 @@ class DeviceSimilarity(GraphedPass):
                 row = np.zeros(len(index), dtype=np.int64)
                 for i, cnt in counts.items():
                     row[i] = cnt
-                kind.append(SIM_CAT)
-                slot.append(len(cat_counts))
                 vocab_n.append(len(strings))
                 cat_counts.append(row)
             else:
                 v = pd.to_numeric(real[name], errors="coerce").to_numpy(dtype=np.float64)
-                kind.append(SIM_NONNEG if name in nonneg else SIM_PLAIN)
-                slot.append(len(cont_vals))
                 cont_vals.append(v[np.isfinite(v)])
-            self.col_of[name] = (kind[-1], slot[-1])
+        self.col_of = {name: (k, sl) for name, k, sl in zip(names, kind, slot)}
         self.order = [n for n in real.columns if n in self.col_of]
-        self.n_cols, self.n_cat, self.n_cont = len(names), len(cat_counts), len(cont_vals)
+        self.n_cat, self.n_cont = len(cat_counts), len(cont_vals)
         dev = self.device
         i32 = dict(dtype=torch.int32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
@@ -177,9 +137,6 @@ class DeviceSimilarity(GraphedPass):
         self.scores = torch.zeros(2 + self.n_cat + self.n_cont, **f64)
         self._jsd = self.scores[2:2 + self.n_cat]
         self._wd = self.scores[2 + self.n_cat:]
-        self.graph = bool(graph) and dev.type == "cuda"
-        self._graphs: Dict[Tuple[int, int], object] = {}
-        self._staged: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ the pass
     def _launch(self, values: torch.Tensor, n: int) -> None:
@@ -190,24 +147,11 @@ class DeviceSimilarity(GraphedPass):
         ops.sim_jsd(self.real_counts, self.counts, self._jsd)
         ops.sim_mean(self.scores, self.n_cat, self.n_cont)
 
+    def _result(self, n: int) -> SimilarityScores:
+        return SimilarityScores(self.scores.clone(), self)
+
     def score(self, values: torch.Tensor) -> SimilarityScores:
         """values: [n, n_cols] float64 on the evaluator's device, as ``generate_decoded`` returns them.  The work is
-        queued on the current stream; the returned scores are device tensors and nothing waits for them."""
-        if values.dim() != 2 or values.shape[1] != self.n_cols or values.dtype != torch.float64:
-            raise ValueError(f"score: expected a float64 [n, {self.n_cols}] table, got {tuple(values.shape)} "
-                             f"{values.dtype}")
-        if values.device != self.keys.device:
-            raise ValueError(f"score: the table is on {values.device}, the evaluator on {self.keys.device}")
-        n = int(values.shape[0])
-        if n < 1 or n > self.max_rows:
-            raise ValueError(f"score: {n} rows; this evaluator's buffers hold 1..{self.max_rows}")
-        values = values.contiguous()
-        if self.graph:
-            self._replay(values, n)
-        else:
-            self._launch(values, n)
-        out = SimilarityScores(self.scores.clone(), self)
-        check = getattr(self.ops, "check", None)
-        if check is not None:
-            check()       # checked native build: a code outside its vocabulary raises here (release: nothing)
-        return out
+        queued on the current stream; the returned scores are device tensors and nothing waits for them.  In the
+        checked native build a code outside its vocabulary raises here."""
+        return super().score(values)

@@ -70,16 +70,12 @@ host round trip, its number of launches a function of ``max_depth`` alone, so it
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
-import pandas as pd
 import torch
 
-from ..data.constants import CATEGORICAL
-from ..data.decode import meta_column_names
-from .device import GraphedPass
-from .privacy import code_real_table
+from .base import TstrEvaluator, column_slots, most_categories
 
 TREE_CONT, TREE_CAT, TREE_TARGET = 0, 1, 2
 MODELS = ("dt", "rf")
@@ -166,7 +162,10 @@ class ForestScores:
         return self._models[model].arrays(int(t))
 
 
-class DeviceForest(GraphedPass):
+class DeviceForest(TstrEvaluator):
+    LIMITS = "max_rows, trees and min_leaf must be >= 1 and seed >= 0"
+    REUSE_REAL_BUFFERS = True
+
     def __init__(self, train_real, test_real, meta: dict, vocabs: Sequence, device, ops=None,
                  target: Optional[str] = None, trees: int = 100, max_depth: int = 12, min_leaf: int = 1, seed: int = 0,
                  max_rows: int = 40000, graph: bool = False, cardinalities: Optional[Sequence[int]] = None,
@@ -174,102 +173,46 @@ class DeviceForest(GraphedPass):
         """train_real / test_real: the real training and held-out rows as DataFrames, or already coded as float64
         [m, n_cols] arrays.  cardinalities: categories per categorical column (in column order, the target
         included), for coded arrays whose codes do not show them all."""
-        if meta.get("date_info"):
-            raise ValueError("DeviceForest: the table has date columns; the decoded table holds their parts, not "
-                             "the dates, so rows would not be comparable")
-        self.device = torch.device(device)
-        if ops is None:
-            if self.device.type == "cuda":
-                from ..ops.hip import HipOps
-                ops = HipOps(self.device)
-            else:
-                from ..ops.ref import TorchOps
-                ops = TorchOps()
-        self.ops = ops
-        self.max_rows, self.trees, self.max_depth = int(max_rows), int(trees), int(max_depth)
+        super().__init__(meta, device, ops, max_rows, graph)
+        ops, self.trees, self.max_depth = self.ops, int(trees), int(max_depth)
         self.min_leaf, self.seed = int(min_leaf), int(seed)
         self.model_names = tuple(m for m in MODELS if m in tuple(models))
         if not self.model_names or set(models) - set(MODELS):
             raise ValueError(f"DeviceForest: models must be a non-empty subset of {MODELS}, got {tuple(models)}")
-        if self.max_rows < 1 or self.trees < 1 or self.min_leaf < 1 or self.seed < 0:
-            raise ValueError("DeviceForest: max_rows, trees and min_leaf must be >= 1 and seed >= 0")
+        if self.trees < 1 or self.min_leaf < 1 or self.seed < 0:
+            raise ValueError(f"DeviceForest: {self.LIMITS}")
         if not 0 <= self.max_depth <= int(ops.TREE_MAX_DEPTH):
             raise ValueError(f"DeviceForest: max_depth {self.max_depth} is outside 0 .. TREE_MAX_DEPTH = "
                              f"{int(ops.TREE_MAX_DEPTH)}")
-        self.names: List[str] = meta_column_names(meta)
-        self.n_cols = len(self.names)
-        self.target = str(target if target is not None else meta.get("target") or "")
-        is_cat = [c["type"] == CATEGORICAL for c in meta["columns"]]
-        if self.target not in self.names or not is_cat[self.names.index(self.target)]:
-            raise ValueError(f"DeviceForest: the target {self.target!r} is not a categorical column of the table; "
-                             "regression targets are not supported")
-        tcol = self.names.index(self.target)
-        coded = []
-        for what, real in (("training", train_real), ("test", test_real)):
-            if isinstance(real, pd.DataFrame):
-                c = code_real_table(real, meta, vocabs)
-                if c.shape[0] != len(real):
-                    raise ValueError(f"DeviceForest: the real {what} table lost rows in coding")
-            else:
-                c = np.ascontiguousarray(np.asarray(real, dtype=np.float64))
-                if c.ndim != 2 or c.shape[1] != self.n_cols:
-                    raise ValueError(f"DeviceForest: expected a coded [m, {self.n_cols}] real {what} table, got "
-                                     f"{c.shape}")
-            if c.shape[0] < 1:
-                raise ValueError(f"DeviceForest: the real {what} table is empty")
-            coded.append(c)
-        pooled = np.concatenate(coded, axis=0)
-        for j, cat in enumerate(is_cat):
-            col = pooled[:, j]
-            if not np.isfinite(col).all() or (cat and (col < 0).any()):
-                raise ValueError(f"DeviceForest: the real column {self.names[j]!r} holds a value that is not a "
-                                 + ("category code" if cat else "finite number"))
-        cat_cols = [j for j, cat in enumerate(is_cat) if cat]
-        if cardinalities is not None and len(cardinalities) != len(cat_cols):
-            raise ValueError(f"DeviceForest: cardinalities needs one entry per categorical column ({len(cat_cols)})")
-        card_all = []
-        for s, j in enumerate(cat_cols):
-            K = 1 + int(pooled[:, j].max())
-            if s < len(vocabs):
-                K = max(K, len(vocabs[s]))
-            if cardinalities is not None:
-                K = max(K, int(cardinalities[s]))
-            card_all.append(K)
-        self.K = card_all[cat_cols.index(tcol)]
+        coded, pooled, card_of = self._real_tables(train_real, test_real, meta, vocabs, target, cardinalities)
         max_bins = int(ops.TREE_MAX_BINS)
-        kind, slot, card, nbins, eoff, edges, feat_names = [], [], [], [], [0], [], []
-        for j, cat in enumerate(is_cat):
-            if j == tcol:
-                kind.append(TREE_TARGET)
-                slot.append(0)
+        kind = [TREE_TARGET if name == self.target else TREE_CAT if cat else TREE_CONT
+                for name, cat in zip(self.names, self.is_cat)]
+        slot, _ = column_slots(kind, {TREE_CAT: TREE_CONT})          # the features are numbered together
+        card, nbins, eoff, edges, feat_names = [], [], [0], [], []
+        for j, k in enumerate(kind):
+            if k == TREE_TARGET:
                 continue
-            slot.append(len(nbins))
             feat_names.append(self.names[j])
-            if cat:
-                kind.append(TREE_CAT)
-                card.append(card_all[cat_cols.index(j)])
+            if k == TREE_CAT:
+                card.append(card_of[j])
                 nbins.append(card[-1] + 1)
             else:
-                kind.append(TREE_CONT)
                 card.append(0)
-                e = bin_edges(pooled[:, j], max_bins)
-                edges.append(e)
-                nbins.append(len(e) + 1)
-            eoff.append(eoff[-1] + (0 if cat else len(edges[-1])))
+                edges.append(bin_edges(pooled[:, j], max_bins))
+                nbins.append(len(edges[-1]) + 1)
+            eoff.append(eoff[-1] + (0 if k == TREE_CAT else len(edges[-1])))
         self.F = len(nbins)
         if self.F < 1 or self.F > int(ops.TREE_MAX_FEATURES):
             raise ValueError(f"DeviceForest: {self.F} feature columns; 1 .. {int(ops.TREE_MAX_FEATURES)} are supported")
         if max(nbins) > max_bins or self.K > int(ops.TREE_MAX_CLASSES):
-            worst = sorted(range(self.F), key=lambda s: -card[s])[:5]
             raise ValueError(
                 f"DeviceForest: a feature with {max(nbins)} bins and {self.K} classes of the target {self.target!r}; "
                 f"the limits are TREE_MAX_BINS = {max_bins} (categories + 1) and TREE_MAX_CLASSES = "
-                f"{int(ops.TREE_MAX_CLASSES)}; the columns with the most categories are "
-                + ", ".join(f"{feat_names[s]!r} ({card[s]})" for s in worst))
+                f"{int(ops.TREE_MAX_CLASSES)}; " + most_categories(feat_names, card))
         self.kinds, self.card_list, self.nbins_list = kind, card, nbins
         self.edges_list = edges
         self.m_feat = max(1, math.isqrt(self.F))
-        self.n_train, self.n_test = int(coded[0].shape[0]), int(coded[1].shape[0])
         self.max_scratch_bytes = int(max_scratch_bytes)
         for rows in (self.n_train, self.max_rows):
             need = rows * (self.F + 4) + sum(model_bytes(self._T(m), rows, self.K, self.max_depth)
@@ -294,27 +237,22 @@ class DeviceForest(GraphedPass):
         self.conf = {m: torch.zeros(K, K, **i32) for m in self.model_names}
         self.real = {m: torch.zeros(2, **f64) for m in self.model_names}
         self.scores = torch.zeros(len(KEYS), **f64)
-        # the held-out rows are binned once; the real training rows are fitted once with the pass of score()
-        self.test = self._table(self.n_test)
-        ops.tree_pack(torch.from_numpy(coded[1]).to(dev), self.kind, self.slot, self.test)
-        self._alloc(self.n_train)
-        self._launch(torch.from_numpy(coded[0]).to(dev), self.n_train)
-        for i, m in enumerate(MODELS):
-            if m in self.real:
-                self.real[m].copy_(self.scores[6 * i:6 * i + 2])
-        self.conf_real = {m: c.clone() for m, c in self.conf.items()}
-        self.scores.zero_()
-        if self.max_rows != self.n_train:
-            self._alloc(self.max_rows)
-        self.graph = bool(graph) and dev.type == "cuda"
-        self._graphs: Dict[Tuple[int, int], object] = {}
-        self._staged = None
+        self._fit_real(*coded)
 
     def _T(self, model: str) -> int:
         return 1 if model == "dt" else self.trees
 
     def _table(self, rows: int) -> TreeTable:
         return TreeTable(rows, self.card, self.edges, self.eoff, self.nbins, self.max_bins, self.K, self.device)
+
+    def _pack(self, values: torch.Tensor, table: TreeTable) -> None:
+        self.ops.tree_pack(values, self.kind, self.slot, table)
+
+    def _keep_real(self) -> None:
+        for i, m in enumerate(MODELS):
+            if m in self.real:
+                self.real[m].copy_(self.scores[6 * i:6 * i + 2])
+        self.conf_real = {m: c.clone() for m, c in self.conf.items()}
 
     def _alloc(self, rows: int) -> None:
         self.train = self._table(rows)
@@ -323,7 +261,7 @@ class DeviceForest(GraphedPass):
     # ------------------------------------------------------------------ the pass
     def _launch(self, values: torch.Tensor, n: int) -> None:
         ops, t = self.ops, self.train
-        ops.tree_pack(values, self.kind, self.slot, t)
+        self._pack(values, t)
         for i, m in enumerate(MODELS):
             if m not in self.models:
                 continue
@@ -333,24 +271,11 @@ class DeviceForest(GraphedPass):
             ops.tree_predict(self.test, self.n_test, t.cw, model, forest, self.conf[m])
             ops.tree_scores(self.conf[m], self.real[m], self.scores[6 * i:6 * i + 6])
 
+    def _result(self, n: int) -> ForestScores:
+        return ForestScores(self.scores.clone(), {m: c.clone() for m, c in self.conf.items()}, self.models)
+
     def score(self, values: torch.Tensor) -> ForestScores:
         """values: [n, n_cols] float64 on the evaluator's device, as ``generate_decoded`` returns them.  The work is
-        queued on the current stream; the returned scores are device tensors and nothing waits for them."""
-        if values.dim() != 2 or values.shape[1] != self.n_cols or values.dtype != torch.float64:
-            raise ValueError(f"score: expected a float64 [n, {self.n_cols}] table, got {tuple(values.shape)} "
-                             f"{values.dtype}")
-        if values.device != self.scores.device:
-            raise ValueError(f"score: the table is on {values.device}, the evaluator on {self.scores.device}")
-        n = int(values.shape[0])
-        if n < 1 or n > self.max_rows:
-            raise ValueError(f"score: {n} rows; this evaluator's buffers hold 1..{self.max_rows}")
-        values = values.contiguous()
-        if self.graph:
-            self._replay(values, n)
-        else:
-            self._launch(values, n)
-        out = ForestScores(self.scores.clone(), {m: c.clone() for m, c in self.conf.items()}, self.models)
-        check = getattr(self.ops, "check", None)
-        if check is not None:
-            check()       # checked native build: an index outside its table raises here (release: nothing)
-        return out
+        queued on the current stream; the returned scores are device tensors and nothing waits for them.  In the
+        checked native build an index outside its table raises here."""
+        return super().score(values)

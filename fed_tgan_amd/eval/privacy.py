@@ -38,7 +38,7 @@ import torch
 from ..data.constants import CATEGORICAL
 from ..data.decode import meta_column_names
 from ..data.table import TablePreprocessor
-from .device import GraphedPass
+from .base import DeviceEvaluator, coded_table, column_slots
 
 NN_CONT, NN_CAT = 0, 1
 KEYS = ("dcr_p5", "nndr_p5", "dcr_min", "copies", "dcr_rr_p5", "nndr_rr_p5")
@@ -92,47 +92,17 @@ def code_real_table(real: pd.DataFrame, meta: dict, vocabs: Sequence) -> np.ndar
     return out
 
 
-class DevicePrivacy(GraphedPass):
+class DevicePrivacy(DeviceEvaluator):
     def __init__(self, real, meta: dict, vocabs: Sequence, device, ops=None, max_rows: int = 40000,
                  baseline: bool = True, graph: bool = False):
         """real: the real table as a DataFrame, or already coded as a float64 [m, n_cols] array."""
-        if meta.get("date_info"):
-            raise ValueError("DevicePrivacy: the table has date columns; the decoded table holds their parts, not "
-                             "the dates, so rows would not be comparable")
-        self.device = torch.device(device)
-        if ops is None:
-            if self.device.type == "cuda":
-                from ..ops.hip import HipOps
-                ops = HipOps(self.device)
-            else:
-                from ..ops.ref import TorchOps
-                ops = TorchOps()
-        self.ops = ops
-        self.max_rows = int(max_rows)
-        if self.max_rows < 1:
-            raise ValueError("DevicePrivacy: max_rows must be >= 1")
-        names = meta_column_names(meta)
-        self.n_cols = len(names)
-        kind = [NN_CAT if c["type"] == CATEGORICAL else NN_CONT for c in meta["columns"]]
-        slot, n_cat, n_cont = [], 0, 0
-        for k in kind:
-            slot.append(n_cat if k == NN_CAT else n_cont)
-            n_cat += k == NN_CAT
-            n_cont += k == NN_CONT
-        self.n_cat, self.n_cont = n_cat, n_cont
-        if isinstance(real, pd.DataFrame):
-            coded = code_real_table(real, meta, vocabs)
-        else:
-            coded = np.ascontiguousarray(np.asarray(real, dtype=np.float64))
-            if coded.ndim != 2 or coded.shape[1] != self.n_cols:
-                raise ValueError(f"DevicePrivacy: expected a coded [m, {self.n_cols}] real table, got {coded.shape}")
-            for j, k in enumerate(kind):
-                if k == NN_CONT and not np.isfinite(coded[:, j]).all():
-                    raise ValueError(f"DevicePrivacy: the real column {names[j]!r} holds a value that is not a "
-                                     "finite number")
+        super().__init__(meta, device, ops, max_rows, graph)
+        ops = self.ops
+        kind = [NN_CAT if cat else NN_CONT for cat in self.is_cat]
+        slot, count = column_slots(kind)
+        self.n_cat, self.n_cont = n_cat, n_cont = count.get(NN_CAT, 0), count.get(NN_CONT, 0)
+        coded = coded_table(real, meta, vocabs, self.who, finite="array")
         m = coded.shape[0]
-        if m < 1:
-            raise ValueError("DevicePrivacy: the real table is empty")
         self.n_real = m
         dev = self.device
         i32 = dict(dtype=torch.int32, device=dev)
@@ -159,9 +129,6 @@ class DevicePrivacy(GraphedPass):
             self.scores[4:6] = self.scores[0:2]
             self.scores[:4] = 0.0
         self._alloc(self.max_rows)
-        self.graph = bool(graph) and dev.type == "cuda"
-        self._graphs: Dict[Tuple[int, int], object] = {}
-        self._staged = None
 
     def _alloc(self, rows: int) -> None:
         ops, dev = self.ops, self.device
@@ -186,21 +153,11 @@ class DevicePrivacy(GraphedPass):
         self.ops.nn_pack(values, self.kind, self.slot, self.lo, self.scale, self.q_cont, self.q_cat)
         self._stats(self.q_cont[:n], self.q_cat[:n], n, False)
 
+    def _result(self, n: int) -> PrivacyScores:
+        return PrivacyScores(self.scores.clone(), self.d1[:n].clone(), self.d2[:n].clone(), self.i1[:n].clone())
+
     def score(self, values: torch.Tensor) -> PrivacyScores:
         """values: [n, n_cols] float64 on the evaluator's device, as ``generate_decoded`` returns them (finite
         values are a precondition).  The work is queued on the current stream; the returned scores are device
         tensors and nothing waits for them."""
-        if values.dim() != 2 or values.shape[1] != self.n_cols or values.dtype != torch.float64:
-            raise ValueError(f"score: expected a float64 [n, {self.n_cols}] table, got {tuple(values.shape)} "
-                             f"{values.dtype}")
-        if values.device != self.keys.device:
-            raise ValueError(f"score: the table is on {values.device}, the evaluator on {self.keys.device}")
-        n = int(values.shape[0])
-        if n < 1 or n > self.max_rows:
-            raise ValueError(f"score: {n} rows; this evaluator's buffers hold 1..{self.max_rows}")
-        values = values.contiguous()
-        if self.graph:
-            self._replay(values, n)
-        else:
-            self._launch(values, n)
-        return PrivacyScores(self.scores.clone(), self.d1[:n].clone(), self.d2[:n].clone(), self.i1[:n].clone())
+        return super().score(values)

@@ -46,16 +46,12 @@ elsewhere; the second is the first's oracle.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
-import pandas as pd
 import torch
 
-from ..data.constants import CATEGORICAL
-from ..data.decode import meta_column_names
-from .device import GraphedPass
-from .privacy import code_real_table
+from .base import TstrEvaluator, column_slots, most_categories
 
 UTIL_CONT, UTIL_CAT, UTIL_TARGET = 0, 1, 2
 KEYS = ("f1_fake", "acc_fake", "f1_real", "acc_real", "f1_gap", "acc_gap", "loss_fake", "grad_fake")
@@ -107,95 +103,36 @@ class UtilityScores:
         return self._W
 
 
-class DeviceUtility(GraphedPass):
+class DeviceUtility(TstrEvaluator):
+    LIMITS = "max_rows must be >= 1 and iters >= 0"
+
     def __init__(self, train_real, test_real, meta: dict, vocabs: Sequence, device, ops=None,
                  target: Optional[str] = None, iters: int = 200, max_rows: int = 40000, graph: bool = False,
                  cardinalities: Optional[Sequence[int]] = None):
         """train_real / test_real: the real training and held-out rows as DataFrames, or already coded as float64
         [m, n_cols] arrays.  cardinalities: categories per categorical column (in column order, the target
         included), for coded arrays whose codes do not show them all."""
-        if meta.get("date_info"):
-            raise ValueError("DeviceUtility: the table has date columns; the decoded table holds their parts, not "
-                             "the dates, so rows would not be comparable")
-        self.device = torch.device(device)
-        if ops is None:
-            if self.device.type == "cuda":
-                from ..ops.hip import HipOps
-                ops = HipOps(self.device)
-            else:
-                from ..ops.ref import TorchOps
-                ops = TorchOps()
-        self.ops = ops
-        self.max_rows, self.iters = int(max_rows), int(iters)
-        if self.max_rows < 1 or self.iters < 0:
-            raise ValueError("DeviceUtility: max_rows must be >= 1 and iters >= 0")
-        self.names: List[str] = meta_column_names(meta)
-        self.n_cols = len(self.names)
-        self.target = str(target if target is not None else meta.get("target") or "")
-        is_cat = [c["type"] == CATEGORICAL for c in meta["columns"]]
-        if self.target not in self.names or not is_cat[self.names.index(self.target)]:
-            raise ValueError(f"DeviceUtility: the target {self.target!r} is not a categorical column of the table; "
-                             "regression targets are not supported")
-        tcol = self.names.index(self.target)
-        coded = []
-        for what, real in (("training", train_real), ("test", test_real)):
-            if isinstance(real, pd.DataFrame):
-                c = code_real_table(real, meta, vocabs)
-                if c.shape[0] != len(real):
-                    raise ValueError(f"DeviceUtility: the real {what} table lost rows in coding")
-            else:
-                c = np.ascontiguousarray(np.asarray(real, dtype=np.float64))
-                if c.ndim != 2 or c.shape[1] != self.n_cols:
-                    raise ValueError(f"DeviceUtility: expected a coded [m, {self.n_cols}] real {what} table, got "
-                                     f"{c.shape}")
-            if c.shape[0] < 1:
-                raise ValueError(f"DeviceUtility: the real {what} table is empty")
-            coded.append(c)
-        pooled = np.concatenate(coded, axis=0)
-        for j, cat in enumerate(is_cat):
-            col = pooled[:, j]
-            if not np.isfinite(col).all() or (cat and (col < 0).any()):
-                raise ValueError(f"DeviceUtility: the real column {self.names[j]!r} holds a value that is not a "
-                                 + ("category code" if cat else "finite number"))
-        cat_cols = [j for j, cat in enumerate(is_cat) if cat]
-        if cardinalities is not None and len(cardinalities) != len(cat_cols):
-            raise ValueError(f"DeviceUtility: cardinalities needs one entry per categorical column ({len(cat_cols)})")
-        card_all = []
-        for s, j in enumerate(cat_cols):
-            K = 1 + int(pooled[:, j].max())
-            if s < len(vocabs):
-                K = max(K, len(vocabs[s]))
-            if cardinalities is not None:
-                K = max(K, int(cardinalities[s]))
-            card_all.append(K)
-        self.K = card_all[cat_cols.index(tcol)]
-        kind, slot, card, feat_names = [], [], [], []
-        n_cont = 0
-        for j, cat in enumerate(is_cat):
-            if j == tcol:
-                kind.append(UTIL_TARGET)
-                slot.append(0)
-            elif cat:
-                kind.append(UTIL_CAT)
-                slot.append(len(card))
-                card.append(card_all[cat_cols.index(j)])
-                feat_names.append(self.names[j])
-            else:
-                kind.append(UTIL_CONT)
-                slot.append(n_cont)
-                n_cont += 1
+        super().__init__(meta, device, ops, max_rows, graph)
+        ops, self.iters = self.ops, int(iters)
+        if self.iters < 0:
+            raise ValueError(f"DeviceUtility: {self.LIMITS}")
+        coded, pooled, card_of = self._real_tables(train_real, test_real, meta, vocabs, target, cardinalities)
+        kind = [UTIL_TARGET if name == self.target else UTIL_CAT if cat else UTIL_CONT
+                for name, cat in zip(self.names, self.is_cat)]
+        slot, count = column_slots(kind)
+        n_cont = count.get(UTIL_CONT, 0)
+        card = [card_of[j] for j, k in enumerate(kind) if k == UTIL_CAT]
+        feat_names = [self.names[j] for j, k in enumerate(kind) if k == UTIL_CAT]
         self.kinds, self.n_cont, self.n_cat, self.card_list = kind, n_cont, len(card), card
         offs = [0]
         for Kc in card:
             offs.append(offs[-1] + Kc + 1)
         self.D = n_cont + offs[-1] + 1
         if self.D > int(ops.UTIL_MAX_FEATURES) or self.K > int(ops.UTIL_MAX_CLASSES):
-            worst = sorted(range(len(card)), key=lambda s: -card[s])[:5]
             raise ValueError(
                 f"DeviceUtility: {self.D} feature columns and {self.K} classes of the target {self.target!r}; the "
                 f"limits are UTIL_MAX_FEATURES = {int(ops.UTIL_MAX_FEATURES)} and UTIL_MAX_CLASSES = "
-                f"{int(ops.UTIL_MAX_CLASSES)}; the columns with the most categories are "
-                + ", ".join(f"{feat_names[s]!r} ({card[s]})" for s in worst))
+                f"{int(ops.UTIL_MAX_CLASSES)}; " + most_categories(feat_names, card))
         cont_cols = [j for j, k in enumerate(kind) if k == UTIL_CONT]
         mean = pooled[:, cont_cols].mean(axis=0) if cont_cols else np.zeros(0)
         sd = pooled[:, cont_cols].std(axis=0) if cont_cols else np.zeros(0)
@@ -218,30 +155,28 @@ class DeviceUtility(GraphedPass):
         self.conf = torch.zeros(K, K, **i32)
         self.real = torch.zeros(2, **f64)
         self.scores = torch.zeros(len(KEYS), **f64)
-        self.n_train, self.n_test = int(coded[0].shape[0]), int(coded[1].shape[0])
-        # the held-out rows are packed once; the real training rows are fitted once with the pass of score()
-        self.test = UtilityTable(self.n_test, n_cont, self.card, self.offs, D, K, dev)
-        ops.util_pack(torch.from_numpy(coded[1]).to(dev), self.kind, self.slot, self.mean, self.sd, self.test)
-        self._alloc(self.n_train)
-        self._launch(torch.from_numpy(coded[0]).to(dev), self.n_train)
+        self._fit_real(*coded)
+
+    def _table(self, rows: int) -> UtilityTable:
+        return UtilityTable(rows, self.n_cont, self.card, self.offs, self.D, self.K, self.device)
+
+    def _pack(self, values: torch.Tensor, table: UtilityTable) -> None:
+        self.ops.util_pack(values, self.kind, self.slot, self.mean, self.sd, table)
+
+    def _keep_real(self) -> None:
         self.real.copy_(self.scores[:2])
         self.W_real, self.conf_real = self.W.clone(), self.conf.clone()
-        self.scores.zero_()
-        self._alloc(self.max_rows)
-        self.graph = bool(graph) and dev.type == "cuda"
-        self._graphs: Dict[Tuple[int, int], object] = {}
-        self._staged = None
 
     def _alloc(self, rows: int) -> None:
         dev, ops = self.device, self.ops
-        self.train = UtilityTable(rows, self.n_cont, self.card, self.offs, self.D, self.K, dev)
+        self.train = self._table(rows)
         self.part = torch.zeros(max(ops.util_part(rows, self.D, self.K), 1), dtype=torch.float64, device=dev)
         self.lossp = torch.zeros((rows + ops.UTIL_CHUNK - 1) // ops.UTIL_CHUNK, dtype=torch.float64, device=dev)
 
     # ------------------------------------------------------------------ the pass
     def _fit(self, values: torch.Tensor, n: int) -> None:
         ops, t = self.ops, self.train
-        ops.util_pack(values, self.kind, self.slot, self.mean, self.sd, t)
+        self._pack(values, t)
         ops.util_gram(t, n, self.M, self.part)
         ops.util_factor(self.M, self.Lt, self.X, self.Minv)
         self.W.zero_()
@@ -255,21 +190,11 @@ class DeviceUtility(GraphedPass):
         self.ops.util_predict(self.test, self.n_test, self.train.counts, self.W, self.conf, self.G, self.loss,
                               self.real, self.scores)
 
+    def _result(self, n: int) -> UtilityScores:
+        return UtilityScores(self.scores.clone(), self.conf.clone(), self.W.clone())
+
     def score(self, values: torch.Tensor) -> UtilityScores:
         """values: [n, n_cols] float64 on the evaluator's device, as ``generate_decoded`` returns them (finite
         values in the continuous columns are a precondition).  The work is queued on the current stream; the
         returned scores are device tensors and nothing waits for them."""
-        if values.dim() != 2 or values.shape[1] != self.n_cols or values.dtype != torch.float64:
-            raise ValueError(f"score: expected a float64 [n, {self.n_cols}] table, got {tuple(values.shape)} "
-                             f"{values.dtype}")
-        if values.device != self.scores.device:
-            raise ValueError(f"score: the table is on {values.device}, the evaluator on {self.scores.device}")
-        n = int(values.shape[0])
-        if n < 1 or n > self.max_rows:
-            raise ValueError(f"score: {n} rows; this evaluator's buffers hold 1..{self.max_rows}")
-        values = values.contiguous()
-        if self.graph:
-            self._replay(values, n)
-        else:
-            self._launch(values, n)
-        return UtilityScores(self.scores.clone(), self.conf.clone(), self.W.clone())
+        return super().score(values)

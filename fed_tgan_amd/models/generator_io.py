@@ -58,11 +58,7 @@ class LoadedGenerator:
     transformer: VGMTransformer
     meta: dict
     vocabs: list
-    _similarity: dict = dataclasses.field(default_factory=dict, repr=False)   # (real table, n) -> its evaluator
-    _privacy: dict = dataclasses.field(default_factory=dict, repr=False)      # the same for privacy()
-    _correlation: dict = dataclasses.field(default_factory=dict, repr=False)  # and for correlation()
-    _utility: dict = dataclasses.field(default_factory=dict, repr=False)      # and for utility()
-    _forest: dict = dataclasses.field(default_factory=dict, repr=False)       # and for tree_utility()
+    _evaluators: dict = dataclasses.field(default_factory=dict, repr=False)   # kind -> (key, real frames, evaluator)
 
     def sample(self, n: int, where=None, max_passes: int = 64) -> np.ndarray:
         """[n, n_columns] decoded values (label codes for categoricals), float64.  A GPU table comes
@@ -156,21 +152,10 @@ class LoadedGenerator:
             self.device_table(n, where=where, max_passes=max_passes)).floats()
 
     def _utility_evaluator(self, train_real, test_real, n: int, iters: int = 200):
-        import pandas as pd
         from ..eval.utility_device import DeviceUtility
-        key = tuple(t if isinstance(t, str) or t is None else id(t) for t in (train_real, test_real)) + (int(n),
-                                                                                                       int(iters))
-        if key not in self._utility:
-            train = pd.read_csv(train_real) if isinstance(train_real, str) else train_real
-            test = pd.read_csv(test_real) if isinstance(test_real, str) else test_real
-            frames = (train, test)
-            if test is None:
-                held = np.arange(len(train)) % 5 == 4
-                train, test = train[~held].reset_index(drop=True), train[held].reset_index(drop=True)
-            self._utility.clear()
-            self._utility[key] = (frames, DeviceUtility(train, test, self.meta, self.vocabs, self.engine.device,
-                                                        ops=self.engine.ops, iters=int(iters), max_rows=int(n)))
-        return self._utility[key][1]
+        return self._cached("utility", (train_real, test_real), (int(n), int(iters)), lambda train, test: DeviceUtility(
+            *self._held_out(train, test), self.meta, self.vocabs, self.engine.device, ops=self.engine.ops,
+            iters=int(iters), max_rows=int(n)))
 
     def tree_utility(self, train_real, test_real=None, n: int = 40000, where=None, trees: int = 100,
                      max_depth: int = 12, seed: int = 0, max_passes: int = 64) -> dict:
@@ -184,22 +169,11 @@ class LoadedGenerator:
 
     def _forest_evaluator(self, train_real, test_real, n: int, trees: int = 100, max_depth: int = 12, seed: int = 0,
                           models=("dt", "rf")):
-        import pandas as pd
         from ..eval.forest_device import DeviceForest
-        key = tuple(t if isinstance(t, str) or t is None else id(t) for t in (train_real, test_real)) + (
-            int(n), int(trees), int(max_depth), int(seed), tuple(models))
-        if key not in self._forest:
-            train = pd.read_csv(train_real) if isinstance(train_real, str) else train_real
-            test = pd.read_csv(test_real) if isinstance(test_real, str) else test_real
-            frames = (train, test)
-            if test is None:
-                held = np.arange(len(train)) % 5 == 4
-                train, test = train[~held].reset_index(drop=True), train[held].reset_index(drop=True)
-            self._forest.clear()
-            self._forest[key] = (frames, DeviceForest(train, test, self.meta, self.vocabs, self.engine.device,
-                                                      ops=self.engine.ops, trees=int(trees), max_depth=int(max_depth),
-                                                      seed=int(seed), max_rows=int(n), models=tuple(models)))
-        return self._forest[key][1]
+        params = (int(n), int(trees), int(max_depth), int(seed), tuple(models))
+        return self._cached("forest", (train_real, test_real), params, lambda train, test: DeviceForest(
+            *self._held_out(train, test), self.meta, self.vocabs, self.engine.device, ops=self.engine.ops,
+            trees=int(trees), max_depth=int(max_depth), seed=int(seed), max_rows=int(n), models=tuple(models)))
 
     def correlation(self, real, n: int = 40000, where=None, max_passes: int = 64) -> dict:
         """Diff. Corr. of n generated rows against ``real`` (a DataFrame or a CSV path): generated and scored on the
@@ -211,15 +185,8 @@ class LoadedGenerator:
             self.device_table(n, where=where, max_passes=max_passes)).floats()
 
     def _correlation_evaluator(self, real, n: int):
-        import pandas as pd
         from ..eval.correlation import DeviceCorrelation
-        key = (real if isinstance(real, str) else id(real), int(n))
-        if key not in self._correlation:
-            frame = pd.read_csv(real) if isinstance(real, str) else real
-            self._correlation.clear()
-            self._correlation[key] = (frame, DeviceCorrelation(frame, self.meta, self.vocabs, self.engine.device,
-                                                               ops=self.engine.ops, max_rows=int(n)))
-        return self._correlation[key][1]
+        return self._table_evaluator("correlation", DeviceCorrelation, real, n)
 
     def privacy(self, real, n: int = 40000, where=None, max_passes: int = 64) -> dict:
         """DCR / NNDR of n generated rows against ``real`` (a DataFrame or a CSV path): generated and scored on the
@@ -229,27 +196,37 @@ class LoadedGenerator:
         return self._privacy_evaluator(real, n).score(self.device_table(n, where=where, max_passes=max_passes)).floats()
 
     def _privacy_evaluator(self, real, n: int):
-        import pandas as pd
         from ..eval.privacy import DevicePrivacy
-        key = (real if isinstance(real, str) else id(real), int(n))
-        if key not in self._privacy:
-            frame = pd.read_csv(real) if isinstance(real, str) else real
-            self._privacy.clear()
-            self._privacy[key] = (frame, DevicePrivacy(frame, self.meta, self.vocabs, self.engine.device,
-                                                       ops=self.engine.ops, max_rows=int(n)))
-        return self._privacy[key][1]
+        return self._table_evaluator("privacy", DevicePrivacy, real, n)
 
     def _evaluator(self, real, n: int):
-        import pandas as pd
         from ..eval.device import DeviceSimilarity
-        key = (real if isinstance(real, str) else id(real), int(n))
-        if key not in self._similarity:
-            frame = pd.read_csv(real) if isinstance(real, str) else real
-            self._similarity.clear()
-            # (the frame is kept with its evaluator, so its id stays its own while the entry lives)
-            self._similarity[key] = (frame, DeviceSimilarity(frame, self.meta, self.vocabs, self.engine.device,
-                                                             ops=self.engine.ops, max_rows=int(n)))
-        return self._similarity[key][1]
+        return self._table_evaluator("similarity", DeviceSimilarity, real, n)
+
+    def _table_evaluator(self, kind: str, cls, real, n: int):
+        return self._cached(kind, (real,), (int(n),), lambda frame: cls(
+            frame, self.meta, self.vocabs, self.engine.device, ops=self.engine.ops, max_rows=int(n)))
+
+    def _cached(self, kind: str, tables, params: tuple, build):
+        """The evaluator of ``kind`` for these real tables (DataFrames, CSV paths or None) and parameters: the one
+        kept from the last call if they are the same, else ``build(*frames)``, which replaces it."""
+        key = tuple(t if isinstance(t, str) or t is None else id(t) for t in tables) + params
+        entry = self._evaluators.get(kind)
+        if entry is None or entry[0] != key:
+            import pandas as pd
+            frames = tuple(pd.read_csv(t) if isinstance(t, str) else t for t in tables)
+            self._evaluators.pop(kind, None)         # (its buffers go before the new one's are allocated)
+            # (the frames are kept with their evaluator, so their ids stay their own while the entry lives)
+            self._evaluators[kind] = entry = (key, frames, build(*frames))
+        return entry[2]
+
+    @staticmethod
+    def _held_out(train, test):
+        """without test rows, the rows of ``train`` with ``index % 5 == 4`` are held out and the rest train"""
+        if test is not None:
+            return train, test
+        held = np.arange(len(train)) % 5 == 4
+        return train[~held].reset_index(drop=True), train[held].reset_index(drop=True)
 
     def device_table(self, n: int, where=None, max_passes: int = 64) -> torch.Tensor:
         """:meth:`sample`'s table where the engine left it: [n, n_columns] float64 on the engine's device"""

@@ -24,6 +24,20 @@ EPI_MASK = 2            # out = acc * ms
 EPI_RELU = 3
 
 
+def _code_or_overflow(v: torch.Tensor, K) -> torch.Tensor:
+    """v where it lies in [0, K) (a code, still to be truncated), else (NaN included) the overflow bin K; K is a
+    number or a tensor that broadcasts against v"""
+    K = torch.as_tensor(K, dtype=v.dtype, device=v.device)
+    return torch.where((v >= 0) & (v < K), v, K.expand_as(v))
+
+
+def _balanced_weights(counts: torch.Tensor):
+    """(n_valid / (present * count_c) per class and 0 for an absent class, n_valid, classes present), float64"""
+    cd, live = counts.to(torch.float64), counts > 0
+    nv, present = cd.sum(), live.sum().to(torch.float64)
+    return torch.where(live, nv / (present * torch.where(live, cd, torch.ones_like(cd))), torch.zeros_like(cd)), nv, present
+
+
 class TorchOps:
     adam_counts_steps = True     # eager Adam bumps its step counter (the HIP sampler does it there)
     name = "torch"
@@ -621,9 +635,7 @@ class TorchOps:
         if kc:
             ks = torch.tensor([sl[c] for c in kc], dtype=torch.long, device=dev)
             v = values[:, torch.tensor(kc, dtype=torch.long, device=dev)]
-            K = card[ks].to(torch.float64)[None, :]
-            ok = (v >= 0) & (v < K)
-            cat_t[ks, :n] = torch.where(ok, v, K.expand_as(v)).t().to(cat_t.dtype)
+            cat_t[ks, :n] = _code_or_overflow(v, card[ks][None, :]).t().to(cat_t.dtype)
 
     def corr_moments(self, cont, cat_t, n, mean, card, offs, G, part=None):
         """G [W, n_cont] = F^T Xc in float64 with Xc = cont[:n] - mean and F = [Xc | one-hot(codes)]: rows
@@ -768,20 +780,13 @@ class TorchOps:
         if kc:
             ks = torch.tensor([sl[c] for c in kc], dtype=torch.long, device=dev)
             v = values[:, torch.tensor(kc, dtype=torch.long, device=dev)]
-            Kc = tab.card[ks].to(torch.float64)[None, :]
-            ok = (v >= 0) & (v < Kc)
-            tab.cat_t[ks, :n] = torch.where(ok, v, Kc.expand_as(v)).t().to(tab.cat_t.dtype)
-        v = values[:, tc[0]]
-        ok = (v >= 0) & (v < K)
-        y = torch.where(ok, v, torch.full_like(v, float(K))).long()
+            tab.cat_t[ks, :n] = _code_or_overflow(v, tab.card[ks][None, :]).t().to(tab.cat_t.dtype)
+        y = _code_or_overflow(values[:, tc[0]], K).long()
         tab.y[:n] = y.to(tab.y.dtype)
         counts = torch.bincount(y, minlength=K + 1)[:K]
         tab.counts.copy_(counts.to(tab.counts.dtype))
-        cd = counts.to(torch.float64)
-        nv, present = cd.sum(), (counts > 0).sum().to(torch.float64)
-        live = counts > 0
-        cw = torch.where(live, nv / (present * torch.where(live, cd, torch.ones_like(cd))), torch.zeros_like(cd))
-        S = (cd * cw).sum()
+        cw, nv, present = _balanced_weights(counts)
+        S = (counts.to(torch.float64) * cw).sum()
         tab.info[0], tab.info[1], tab.info[3] = nv, present, 0.0
         tab.info[2] = torch.where(S > 0, S, torch.ones_like(S))
         tab.s[:n] = torch.cat([cw, cw.new_zeros(1)])[y]
@@ -940,17 +945,13 @@ class TorchOps:
                 tab.bins[f, :n] = b.clamp(max=self.TREE_MAX_BINS - 1).to(torch.uint8)
                 continue
             Kc = K if k == self.TREE_TARGET else card[f]
-            ok = (v >= 0) & (v < Kc)
-            code = torch.where(ok, torch.where(ok, v, torch.zeros_like(v)).long(), torch.full_like(v, Kc, dtype=torch.int64))
+            code = _code_or_overflow(v, Kc).long()
             if k == self.TREE_TARGET:
                 tab.y[:n] = code.to(torch.int32)
-                tab.counts.copy_(torch.bincount(code[ok], minlength=K)[:K].to(torch.int32))
+                tab.counts.copy_(torch.bincount(code, minlength=K + 1)[:K].to(torch.int32))
             else:
                 tab.bins[f, :n] = code.to(torch.uint8)
-        cnt = tab.counts.to(torch.float64)
-        nv, present = tab.counts.sum().to(torch.float64), (tab.counts > 0).sum().to(torch.float64)
-        tab.cw.copy_(torch.where(cnt > 0, nv / (present * torch.where(cnt > 0, cnt, torch.ones_like(cnt))),
-                                 torch.zeros_like(cnt)))
+        tab.cw.copy_(_balanced_weights(tab.counts)[0])
 
     def tree_bootstrap(self, mult, n, bootstrap, seed):
         """mult [T, >= n] int32: 1 per row, or with ``bootstrap`` how often tree t drew the row among its n draws,
