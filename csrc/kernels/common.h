@@ -136,7 +136,9 @@ __device__ __forceinline__ uint4 rng4(const RngArgs& rng, uint64_t step, uint64_
   return philox4x32_10(c, k);
 }
 
-// uniform in (0, 1): never exactly 0 or 1 (safe for log(-log(u)) and Box-Muller)
+// uniform on the 24-bit grid, range [2^-25, 1.0]: never 0, but for x >> 8 == 0xFFFFFF the sum 16777215.5 is a tie
+// that rounds to 16777216, so the value is exactly 1.0 with probability 2^-24.  Every consumer clamps: min(.., n - 1)
+// on u01 * n, the `w - 1` fall-through of the CDF search, the fmaxf in neg_log_u, and `u >= p_drop` keeps the element
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 __device__ __forceinline__ double u01d(uint32_t a, uint32_t b) {

@@ -53,6 +53,18 @@ from .samplers import CondTables, RowIndex
 EPI_NONE, EPI_LRELU_DROPOUT, EPI_MASK, EPI_RELU = 0, 1, 2, 3
 
 
+def d_dropout_stream(stream_base: int, layer: int) -> int:
+    """Philox stream of D layer ``layer``'s dropout mask in the phase whose D forward has ``stream_base`` (4: the D
+    phase, 14: the G phase).  The GEMM receives this number as it is, while every other kernel receives its call
+    site's id times 16 (the sampler uses four from there), see docs/ARCHITECTURE.md.  Layers 0 and 1 keep
+    ``stream_base + layer``; from layer 2 on that sequence would run into the G phase's bases and, at 14 + 2, into the
+    D-phase sampler's block 16..19, so deeper layers draw inside the block ``16 * stream_base + [2, 16)`` -- the block
+    of a call-site id that only the GEMMs use."""
+    if not 0 <= layer < 16:
+        raise ValueError(f"D layer {layer}: dropout streams are laid out for at most 16 layers")
+    return stream_base + layer if layer < 2 else 16 * stream_base + layer
+
+
 def _ext(t: torch.Tensor, cols: int) -> torch.Tensor:
     """Widen a row-strided 2-D view to ``cols`` columns, into its storage's zero padding."""
     if t.shape[1] == cols:
@@ -693,7 +705,7 @@ class CTGANEngine(GenerationMixin):
                        p_drop=self.cfg.dropout_p, stream_id=stream_base + 1, head=h1, group=4)
             o.gemm(inp, self.p[f"D.{i}.W"], self.dl[i][rows], tb=True, bias=self.p[f"D.{i}.b"], epi=EPI_LRELU_DROPOUT,
                    ms=self.ms[i][rows], slope=self.cfg.lrelu_slope, p_drop=self.cfg.dropout_p,
-                   stream_id=stream_base + i, head=head, **kw)
+                   stream_id=d_dropout_stream(stream_base, i), head=head, **kw)
             if chain:
                 break
             inp = self.dl[i][rows]

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from fed_tgan_amd.ops.ref import TorchOps
+from helpers import table_spans as _spans, wide_spans as _wide_spans
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -200,14 +201,6 @@ def test_gp_scale_dhead_colsum(hip):
     assert torch.allclose(o1, o2, atol=1e-6, rtol=1e-4) and torch.allclose(l1, l2, rtol=1e-4)
     assert torch.allclose(y1, y2, atol=1e-4) and torch.allclose(a1, a2) and torch.allclose(m1, m2, atol=1e-4)
     assert torch.allclose(c1, c2, atol=1e-4)
-
-
-def _spans():
-    from helpers import small_table
-    _, _, _, _, _, _, tr, X = small_table()
-    spans = [(int(s), int(w), int(k)) for s, w, k in zip(tr.layout.start, tr.layout.width, tr.layout.kind)]
-    cond = [(int(s), int(w)) for s, w in zip(tr.layout.cond_start, tr.layout.cond_width)]
-    return tr, X, spans, cond
 
 
 def test_activate_statistics(hip):
@@ -493,21 +486,6 @@ def test_gemm_split_counts(hip, splits):
     torch.cuda.synchronize()
     ref = torch.relu(a.double() @ b.double().t() + bias.double()).float()
     assert ((c - ref).norm() / ref.norm()).item() < 1e-2
-
-
-def _wide_spans(D_min=1500, seed=0):
-    """Synthetic layout wider than the register-prefetch path (D > 512): tanh + softmax spans,
-    some wider than a wave."""
-    rng = np.random.default_rng(seed)
-    spans, cond, pos = [], [], 0
-    while pos < D_min:
-        spans.append((pos, 1, 0))
-        pos += 1
-        w = int(rng.choice([2, 3, 7, 13, 70, 130]))
-        spans.append((pos, w, 1))
-        cond.append((pos, w))
-        pos += w
-    return spans, cond, pos
 
 
 def test_wide_activation_and_backward(hip):
