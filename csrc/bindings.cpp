@@ -1567,6 +1567,77 @@ int64_t util_chunk() { return fedtgan::UTIL_CHUNK; }
 int64_t util_part(int64_t n_max, int64_t D, int64_t K) { return fedtgan::util_part_doubles(n_max, D, K); }
 int64_t util_groups(int64_t n, int64_t cells) { return fedtgan::util_groups(n, cells).groups; }
 
+// ----------------------------------------------------------------------------- MLP-utility evaluator
+namespace {
+void mlp_check_theta(const char* what, const Tensor& theta, int64_t D, int64_t H, int64_t K) {
+  TORCH_CHECK(H >= 1 && H <= fedtgan::MLP_MAX_HIDDEN, what, ": H must be 1 .. MLP_MAX_HIDDEN");
+  TORCH_CHECK(sim_f64(theta) && theta.numel() == D * H + (H + 1) * K, what, ": float64 [D H + (H + 1) K] expected");
+}
+}  // namespace
+
+void mlp_step(const Tensor& cont, const Tensor& cat_t, const Tensor& y, const Tensor& s, const Tensor& counts,
+              const Tensor& info, const Tensor& card, const Tensor& offs, int64_t n, int64_t D, int64_t b, int64_t nb,
+              const Tensor& theta, const Tensor& mom, const Tensor& var, const Tensor& h, const Tensor& dz,
+              const Tensor& dh, const Tensor& cnt, int64_t H, double alpha, double lr_t) {
+  fedtgan::MlpStepArgs a{};
+  a.t = util_table("mlp_step", cont, cat_t, y, s, counts, info, card, offs, n, D);
+  const int64_t K = counts.numel();
+  mlp_check_theta("mlp_step: theta", theta, D, H, K);
+  mlp_check_theta("mlp_step: m", mom, D, H, K);
+  mlp_check_theta("mlp_step: v", var, D, H, K);
+  TORCH_CHECK(nb >= 1 && nb <= n && b >= 0 && b < nb, "mlp_step: batch b of nb, 0 <= b < nb <= n");
+  const int64_t rows = fedtgan::mlp_batch_rows(n, b, nb), blocks = (rows + fedtgan::MLP_ROWS - 1) / fedtgan::MLP_ROWS;
+  TORCH_CHECK(rows >= 1 && rows <= fedtgan::MLP_MAX_BATCH, "mlp_step: a batch of ", rows,
+              " rows; MLP_MAX_BATCH = ", fedtgan::MLP_MAX_BATCH);
+  TORCH_CHECK(sim_f64(h) && h.numel() >= rows * H && sim_f64(dh) && dh.numel() >= rows * H && sim_f64(dz) &&
+                  dz.numel() >= rows * K && sim_i32(cnt) && cnt.numel() >= blocks,
+              "mlp_step: scratch h / dh float64 [rows, H], dz float64 [rows, K], cnt int32 [row blocks] for ", rows,
+              " rows");
+  a.b = (int)b;
+  a.nb = (int)nb;
+  a.H = (int)H;
+  a.theta = theta.data_ptr<double>();
+  a.mom = mom.data_ptr<double>();
+  a.var = var.data_ptr<double>();
+  a.h = h.data_ptr<double>();
+  a.dz = dz.data_ptr<double>();
+  a.dh = dh.data_ptr<double>();
+  a.cnt = cnt.data_ptr<int>();
+  a.alpha = alpha;
+  a.lr_t = lr_t;
+  fedtgan::launch_mlp_step(a, cur_stream());
+}
+
+void mlp_loss(const Tensor& cont, const Tensor& cat_t, const Tensor& y, const Tensor& s, const Tensor& counts,
+              const Tensor& info, const Tensor& card, const Tensor& offs, int64_t n, int64_t D, const Tensor& theta,
+              int64_t H, double alpha, const Tensor& loss) {
+  const fedtgan::UtilTable t = util_table("mlp_loss", cont, cat_t, y, s, counts, info, card, offs, n, D);
+  mlp_check_theta("mlp_loss: theta", theta, D, H, counts.numel());
+  const int64_t need = 1 + (n + fedtgan::MLP_ROWS - 1) / fedtgan::MLP_ROWS;
+  TORCH_CHECK(sim_f64(loss) && loss.numel() >= need, "mlp_loss: loss needs ", need, " float64");
+  fedtgan::launch_mlp_loss(t, theta.data_ptr<double>(), (int)H, alpha, loss.data_ptr<double>(), cur_stream());
+}
+
+void mlp_predict(const Tensor& cont, const Tensor& cat_t, const Tensor& y, const Tensor& s, const Tensor& counts,
+                 const Tensor& info, const Tensor& card, const Tensor& offs, int64_t n, int64_t D,
+                 const Tensor& train_counts, const Tensor& theta, int64_t H, const Tensor& conf, const Tensor& loss,
+                 const Tensor& real, const Tensor& out) {
+  const fedtgan::UtilTable t = util_table("mlp_predict", cont, cat_t, y, s, counts, info, card, offs, n, D);
+  const int64_t K = counts.numel();
+  mlp_check_theta("mlp_predict: theta", theta, D, H, K);
+  TORCH_CHECK(sim_i32(train_counts) && train_counts.numel() == K && sim_i32(conf) && conf.numel() == K * K,
+              "mlp_predict: train_counts int32 [K], conf int32 [K, K]");
+  TORCH_CHECK(sim_f64(loss) && loss.numel() >= 1 && sim_f64(real) && real.numel() >= 2 && sim_f64(out) &&
+                  out.numel() >= 7, "mlp_predict: loss [1], real [2], out [7] float64");
+  fedtgan::launch_mlp_predict(t, train_counts.data_ptr<int>(), theta.data_ptr<double>(), (int)H, conf.data_ptr<int>(),
+                              loss.data_ptr<double>(), real.data_ptr<double>(), out.data_ptr<double>(), cur_stream());
+}
+
+int64_t mlp_max_hidden() { return fedtgan::MLP_MAX_HIDDEN; }
+int64_t mlp_max_batch() { return fedtgan::MLP_MAX_BATCH; }
+int64_t mlp_max_steps() { return fedtgan::MLP_MAX_STEPS; }
+int64_t mlp_rows() { return fedtgan::MLP_ROWS; }
+
 // ----------------------------------------------------------------------------- tree-utility evaluator
 namespace {
 bool tree_u8(const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kByte && t.is_contiguous(); }
@@ -2225,6 +2296,17 @@ TORCH_LIBRARY(fedtgan, m) {
   m.def("util_chunk() -> int", &util_chunk);
   m.def("util_part(int n_max, int D, int K) -> int", &util_part);
   m.def("util_groups(int n, int cells) -> int", &util_groups);
+  m.def(
+      "mlp_step(Tensor cont, Tensor cat_t, Tensor y, Tensor s, Tensor counts, Tensor info, Tensor card, Tensor offs, int n, int D, int b, int nb, Tensor(a!) theta, Tensor(b!) m, Tensor(c!) v, Tensor(d!) h, Tensor(e!) dz, "
+      "Tensor(f!) dh, Tensor(g!) cnt, int H, float alpha, float lr_t) -> ()");
+  m.def("mlp_loss(Tensor cont, Tensor cat_t, Tensor y, Tensor s, Tensor counts, Tensor info, Tensor card, Tensor offs, int n, int D, Tensor theta, int H, float alpha, Tensor(a!) loss) -> ()");
+  m.def(
+      "mlp_predict(Tensor cont, Tensor cat_t, Tensor y, Tensor s, Tensor counts, Tensor info, Tensor card, Tensor offs, int n, int D, Tensor train_counts, Tensor theta, int H, Tensor(a!) conf, Tensor loss, Tensor real, "
+      "Tensor(b!) out) -> ()");
+  m.def("mlp_max_hidden() -> int", &mlp_max_hidden);
+  m.def("mlp_max_batch() -> int", &mlp_max_batch);
+  m.def("mlp_max_steps() -> int", &mlp_max_steps);
+  m.def("mlp_rows() -> int", &mlp_rows);
   m.def("tree_pack(Tensor values, Tensor kind, Tensor slot, Tensor card, Tensor edges, Tensor eoff, Tensor(a!) bins, Tensor(b!) y, Tensor(c!) counts, Tensor(d!) cw) -> ()");
   m.def("tree_bootstrap(Tensor(a!) mult, int n, bool bootstrap, int seed) -> ()");
   m.def(
@@ -2311,6 +2393,9 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("util_grad", &util_grad);
   m.impl("util_step", &util_step);
   m.impl("util_predict", &util_predict);
+  m.impl("mlp_step", &mlp_step);
+  m.impl("mlp_loss", &mlp_loss);
+  m.impl("mlp_predict", &mlp_predict);
   m.impl("tree_pack", &tree_pack);
   m.impl("tree_bootstrap", &tree_bootstrap);
   m.impl("tree_grow", &tree_grow);

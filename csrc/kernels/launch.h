@@ -671,6 +671,41 @@ void launch_util_update(double* V, double* W, const double* Minv, const double* 
 void launch_util_predict(const UtilTable& t, const int* train_counts, const double* W, int* conf, const double* G,
                          const double* loss, const double* real, double* out, hipStream_t stream);
 
+// MLP-utility evaluator (kernels/mlp.hip): a one-hidden-layer network h = relu(F W1), z = [h | 1] W2 trained on a packed
+// table (UtilTable, unweighted: only y and counts are read) by a fixed number of Adam steps over strided batches, its
+// loss and its confusion matrix on held-out rows (eval/mlp_device.py has the definition).  All fp64; every sum has an
+// order fixed by the shapes alone, counting is in integers; no floating-point atomics, no allocation, no host round
+// trip.  The limits: a block of 64 rows keeps its h [64, H] (65 KiB at the limit) and its logits [64, K] (33 KiB) in
+// LDS, one workgroup per CU; a batch is at most 16 such blocks.
+constexpr int MLP_MAX_HIDDEN = 128;         // H
+constexpr int MLP_MAX_BATCH = 1024;         // rows of a batch
+constexpr int MLP_MAX_STEPS = 10000;        // steps of a fit (the evaluator's limit: two graph nodes each)
+constexpr int MLP_ROWS = 64;                // rows of a block
+// theta = [W1 [D, H] | W2 [H + 1, K]] flat, the last rows the biases; mom / var: Adam's moments, the same shape
+struct MlpStepArgs {
+  UtilTable t;
+  int b, nb;              // the batch: rows b, b + nb, b + 2 nb, ... < t.n
+  int H;
+  double* theta;
+  double* mom;
+  double* var;
+  double* h;              // [rows of the batch, H]
+  double* dz;             // [rows of the batch, K]
+  double* dh;             // [rows of the batch, H]
+  int* cnt;               // [row blocks of the batch] valid rows
+  double alpha, lr_t;     // L2 penalty; lr sqrt(1 - 0.999^t) / (1 - 0.9^t)
+};
+inline int mlp_batch_rows(int64_t n, int64_t b, int64_t nb) { return (int)((n - b + nb - 1) / nb); }
+// one Adam step on the batch: forward / backward over its row blocks, then one gradient tile + Adam per wave
+void launch_mlp_step(const MlpStepArgs& a, hipStream_t stream);
+// loss[0] = (sum over the valid rows of CE + alpha / 2 |W1, W2 without their bias rows|^2) / max(valid rows, 1);
+// loss[1 ..] : the row blocks' partial sums (scratch, ceil(n / 64) of them)
+void launch_mlp_loss(const UtilTable& t, const double* theta, int H, double alpha, double* loss, hipStream_t stream);
+// conf [K, K] int32 of the rows of t (classes with train_counts == 0 are never predicted);
+// out[0..6] = f1, acc, real[0], real[1], real[0] - f1, real[1] - acc, loss[0]
+void launch_mlp_predict(const UtilTable& t, const int* train_counts, const double* theta, int H, int* conf,
+                        const double* loss, const double* real, double* out, hipStream_t stream);
+
 // Tree-utility evaluator (kernels/forest.hip): a histogram decision tree and a random forest fitted on the binned
 // decoded table, and their confusion matrices on held-out rows (eval/forest_device.py has the definition).  Counting
 // is in integers, the criterion is fp64 in a fixed order without contraction, so a fit is bit-identical on every run.

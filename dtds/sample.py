@@ -44,19 +44,26 @@ def main(argv=None):
     p.add_argument("-utility_test", default=None, metavar="TEST.csv",
                    help="the held-out real rows of -utility_against (default: its rows with index %% 5 == 4)")
     p.add_argument("-utility_iters", type=int, default=200, help="solver iterations of -utility_against")
-    p.add_argument("-utility_models", default="lr", metavar="lr,dt,rf",
+    p.add_argument("-utility_models", default="lr", metavar="lr,dt,rf,mlp",
                    help="the classifiers of -utility_against: lr (logistic regression), dt (histogram decision tree), "
-                        "rf (random forest); the trees' scores join the same JSON line as dt_* / rf_* keys")
+                        "rf (random forest), mlp (one hidden layer); the trees' and the network's scores join the same "
+                        "JSON line as dt_* / rf_* / mlp_* keys")
     p.add_argument("-utility_trees", type=int, default=100, help="trees of the random forest of -utility_models")
     p.add_argument("-utility_depth", type=int, default=12, help="depth limit of the trees of -utility_models")
+    p.add_argument("-utility_hidden", type=int, default=100, help="hidden units of the mlp of -utility_models")
+    p.add_argument("-utility_steps", type=int, default=1000, help="Adam steps of the mlp of -utility_models")
+    p.add_argument("-utility_batch", type=int, default=512, help="rows per batch of the mlp of -utility_models")
     args = p.parse_args(argv)
     if (args.utility_test or args.utility_iters != 200) and not args.utility_against:
         p.error("-utility_test / -utility_iters need -utility_against")
     utility_models = tuple(m for m in args.utility_models.split(",") if m)
-    if not utility_models or set(utility_models) - {"lr", "dt", "rf"}:
-        p.error("-utility_models is a comma-separated subset of lr,dt,rf")
+    if not utility_models or set(utility_models) - {"lr", "dt", "rf", "mlp"}:
+        p.error("-utility_models is a comma-separated subset of lr,dt,rf,mlp")
     if (utility_models != ("lr",) or args.utility_trees != 100 or args.utility_depth != 12) and not args.utility_against:
         p.error("-utility_models / -utility_trees / -utility_depth need -utility_against")
+    if (args.utility_hidden != 100 or args.utility_steps != 1000 or args.utility_batch != 512) and \
+            not args.utility_against:
+        p.error("-utility_hidden / -utility_steps / -utility_batch need -utility_against")
     import torch
     from fed_tgan_amd.models.conditional import parse_where
     from fed_tgan_amd.models.generator_io import load_generator
@@ -71,7 +78,8 @@ def main(argv=None):
             out, args.n, score_real=args.score_against, privacy_real=args.privacy_against,
             corr_real=args.corr_against, where=where or None, max_passes=args.max_passes,
             utility_real=args.utility_against, utility_test=args.utility_test, utility_iters=args.utility_iters,
-            utility_models=utility_models, utility_trees=args.utility_trees, utility_depth=args.utility_depth)
+            utility_models=utility_models, utility_trees=args.utility_trees, utility_depth=args.utility_depth,
+            utility_hidden=args.utility_hidden, utility_steps=args.utility_steps, utility_batch=args.utility_batch)
     else:
         gen.write_csv(out, args.n, where=where or None, max_passes=args.max_passes)
     cond = ""

@@ -2,7 +2,7 @@
 table and tested on real rows (TSTR); the gap to the same models trained on the real training rows is reported.
 
 :class:`fed_tgan_amd.eval.utility_device.DeviceUtility` covers the reference's logistic regression; this evaluator
-covers its two tree models (the MLP stays with ``eval/utility.py``).  Rows live in the space of the decoded table
+covers its two tree models (the MLP is ``eval/mlp_device.py``).  Rows live in the space of the decoded table
 (``generate_decoded``'s ``[n, n_cols]`` float64: label codes in the categorical columns, log1p values in the
 ``non_negative_cols``); the real tables are brought there with :func:`fed_tgan_amd.eval.privacy.code_real_table`.
 Tables with date columns, non-finite real values or a target that is not categorical are refused, and ``K`` and every

@@ -3,8 +3,8 @@ same classifier trained on the real training rows.
 
 Avg_JSD / Avg_WD, DCR / NNDR and Diff. Corr. compare the tables; this evaluator asks whether a model fitted on the
 generated rows classifies held-out real rows.  The classifier is a class-balanced, L2-regularised multinomial logistic
-regression; the reference's decision tree and random forest are ``eval/forest_device.py``, its MLP stays with
-``eval/utility.py`` (sklearn on a CSV).
+regression; the reference's decision tree and random forest are ``eval/forest_device.py``, its MLP
+``eval/mlp_device.py``.
 Rows live in the space of the decoded table (``generate_decoded``'s ``[n, n_cols]`` float64: label codes in the
 categorical columns, log1p values in the ``non_negative_cols``); the real tables are brought there with
 :func:`fed_tgan_amd.eval.privacy.code_real_table`.
@@ -103,20 +103,13 @@ class UtilityScores:
         return self._W
 
 
-class DeviceUtility(TstrEvaluator):
-    LIMITS = "max_rows must be >= 1 and iters >= 0"
+class PackedFeatures:
+    """What the evaluators that train on the packed feature table share (a mixin of a :class:`TstrEvaluator`): the
+    columns' ``kind`` / ``slot``, the one-hot blocks' ``card`` / ``offs``, the standardisation ``mean`` / ``sd``, ``D``
+    and its limits, and the table's allocation and packing."""
 
-    def __init__(self, train_real, test_real, meta: dict, vocabs: Sequence, device, ops=None,
-                 target: Optional[str] = None, iters: int = 200, max_rows: int = 40000, graph: bool = False,
-                 cardinalities: Optional[Sequence[int]] = None):
-        """train_real / test_real: the real training and held-out rows as DataFrames, or already coded as float64
-        [m, n_cols] arrays.  cardinalities: categories per categorical column (in column order, the target
-        included), for coded arrays whose codes do not show them all."""
-        super().__init__(meta, device, ops, max_rows, graph)
-        ops, self.iters = self.ops, int(iters)
-        if self.iters < 0:
-            raise ValueError(f"DeviceUtility: {self.LIMITS}")
-        coded, pooled, card_of = self._real_tables(train_real, test_real, meta, vocabs, target, cardinalities)
+    def _setup_features(self, pooled: np.ndarray, card_of: Dict[int, int]) -> None:
+        ops = self.ops
         kind = [UTIL_TARGET if name == self.target else UTIL_CAT if cat else UTIL_CONT
                 for name, cat in zip(self.names, self.is_cat)]
         slot, count = column_slots(kind)
@@ -130,22 +123,47 @@ class DeviceUtility(TstrEvaluator):
         self.D = n_cont + offs[-1] + 1
         if self.D > int(ops.UTIL_MAX_FEATURES) or self.K > int(ops.UTIL_MAX_CLASSES):
             raise ValueError(
-                f"DeviceUtility: {self.D} feature columns and {self.K} classes of the target {self.target!r}; the "
+                f"{self.who}: {self.D} feature columns and {self.K} classes of the target {self.target!r}; the "
                 f"limits are UTIL_MAX_FEATURES = {int(ops.UTIL_MAX_FEATURES)} and UTIL_MAX_CLASSES = "
                 f"{int(ops.UTIL_MAX_CLASSES)}; " + most_categories(feat_names, card))
         cont_cols = [j for j, k in enumerate(kind) if k == UTIL_CONT]
         mean = pooled[:, cont_cols].mean(axis=0) if cont_cols else np.zeros(0)
         sd = pooled[:, cont_cols].std(axis=0) if cont_cols else np.zeros(0)
         sd = np.where(sd > 0, sd, 1.0)
-        dev = self.device
-        i32 = dict(dtype=torch.int32, device=dev)
-        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        f64 = dict(dtype=torch.float64, device=self.device)
         self.kind = torch.tensor(kind, **i32)
         self.slot = torch.tensor(slot, **i32)
         self.card = torch.tensor(card, **i32)
         self.offs = torch.tensor(offs, **i32)
         self.mean = torch.tensor(mean, **f64)
         self.sd = torch.tensor(sd, **f64)
+
+    def _table(self, rows: int) -> UtilityTable:
+        return UtilityTable(rows, self.n_cont, self.card, self.offs, self.D, self.K, self.device)
+
+    def _pack(self, values: torch.Tensor, table: UtilityTable) -> None:
+        self.ops.util_pack(values, self.kind, self.slot, self.mean, self.sd, table)
+
+
+class DeviceUtility(PackedFeatures, TstrEvaluator):
+    LIMITS = "max_rows must be >= 1 and iters >= 0"
+
+    def __init__(self, train_real, test_real, meta: dict, vocabs: Sequence, device, ops=None,
+                 target: Optional[str] = None, iters: int = 200, max_rows: int = 40000, graph: bool = False,
+                 cardinalities: Optional[Sequence[int]] = None):
+        """train_real / test_real: the real training and held-out rows as DataFrames, or already coded as float64
+        [m, n_cols] arrays.  cardinalities: categories per categorical column (in column order, the target
+        included), for coded arrays whose codes do not show them all."""
+        super().__init__(meta, device, ops, max_rows, graph)
+        self.iters = int(iters)
+        if self.iters < 0:
+            raise ValueError(f"DeviceUtility: {self.LIMITS}")
+        coded, pooled, card_of = self._real_tables(train_real, test_real, meta, vocabs, target, cardinalities)
+        self._setup_features(pooled, card_of)
+        dev = self.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
         self.betas = momentum_table(self.iters)
         D, K = self.D, self.K
         self.M, self.Minv = torch.zeros(D, D, **f64), torch.zeros(D, D, **f64)
@@ -156,12 +174,6 @@ class DeviceUtility(TstrEvaluator):
         self.real = torch.zeros(2, **f64)
         self.scores = torch.zeros(len(KEYS), **f64)
         self._fit_real(*coded)
-
-    def _table(self, rows: int) -> UtilityTable:
-        return UtilityTable(rows, self.n_cont, self.card, self.offs, self.D, self.K, self.device)
-
-    def _pack(self, values: torch.Tensor, table: UtilityTable) -> None:
-        self.ops.util_pack(values, self.kind, self.slot, self.mean, self.sd, table)
 
     def _keep_real(self) -> None:
         self.real.copy_(self.scores[:2])

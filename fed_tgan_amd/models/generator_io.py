@@ -114,31 +114,38 @@ class LoadedGenerator:
 
     def write_csv_all(self, path: str, n: int, score_real=None, privacy_real=None, corr_real=None, threads: int = 0,
                       where=None, max_passes: int = 64, utility_real=None, utility_test=None, utility_iters: int = 200,
-                      utility_models=("lr",), utility_trees: int = 100, utility_depth: int = 12):
+                      utility_models=("lr",), utility_trees: int = 100, utility_depth: int = 12,
+                      utility_hidden: int = 100, utility_steps: int = 1000, utility_batch: int = 512):
         """:meth:`write_csv` with whichever of :meth:`score` (score_real), :meth:`privacy` (privacy_real),
         :meth:`correlation` (corr_real) and :meth:`utility` (utility_real, utility_test) are asked for, all of the
         rows the CSV holds and all taken on the device before the copy.  utility_models: ``"lr"`` (:meth:`utility`)
-        and / or ``"dt"`` / ``"rf"`` (:meth:`tree_utility`, with utility_trees and utility_depth), whose keys share
-        the utility dict.  Returns ((Avg_JSD, Avg_WD) | None, privacy dict | None, correlation dict | None, utility
+        and / or ``"dt"`` / ``"rf"`` (:meth:`tree_utility`, with utility_trees and utility_depth) and / or ``"mlp"``
+        (:meth:`mlp_utility`, with utility_hidden, utility_steps and utility_batch), whose keys share the utility dict
+        in that order.  Returns ((Avg_JSD, Avg_WD) | None, privacy dict | None, correlation dict | None, utility
         dict | None)."""
         utility_models = tuple(utility_models)
-        if not utility_models or set(utility_models) - {"lr", "dt", "rf"}:
-            raise ValueError(f"utility_models must be a non-empty subset of ('lr', 'dt', 'rf'), got {utility_models}")
+        if not utility_models or set(utility_models) - {"lr", "dt", "rf", "mlp"}:
+            raise ValueError("utility_models must be a non-empty subset of ('lr', 'dt', 'rf', 'mlp'), got "
+                             f"{utility_models}")
         vals = self.device_table(n, where=where, max_passes=max_passes)
         sim = self._evaluator(score_real, n).score(vals) if score_real is not None else None
         priv = self._privacy_evaluator(privacy_real, n).score(vals) if privacy_real is not None else None
         corr = self._correlation_evaluator(corr_real, n).score(vals) if corr_real is not None else None
-        util = forest = None
+        util = forest = mlp = None
         if utility_real is not None and "lr" in utility_models:
             util = self._utility_evaluator(utility_real, utility_test, n, utility_iters).score(vals)
         tree_models = tuple(m for m in ("dt", "rf") if m in utility_models)
         if utility_real is not None and tree_models:
             forest = self._forest_evaluator(utility_real, utility_test, n, utility_trees, utility_depth, 0,
                                             tree_models).score(vals)
+        if utility_real is not None and "mlp" in utility_models:
+            mlp = self._mlp_evaluator(utility_real, utility_test, n, utility_hidden, utility_steps,
+                                      utility_batch).score(vals)
         self._write_values(path, self._to_host(vals), threads)
         out = [s.floats() if s is not None else None for s in (sim, priv, corr, util)]
-        if forest is not None:
-            out[3] = dict(out[3] or {}, **forest.floats())
+        for more in (forest, mlp):
+            if more is not None:
+                out[3] = dict(out[3] or {}, **more.floats())
         return tuple(out)
 
     def utility(self, train_real, test_real=None, n: int = 40000, where=None, max_passes: int = 64,
@@ -174,6 +181,24 @@ class LoadedGenerator:
         return self._cached("forest", (train_real, test_real), params, lambda train, test: DeviceForest(
             *self._held_out(train, test), self.meta, self.vocabs, self.engine.device, ops=self.engine.ops,
             trees=int(trees), max_depth=int(max_depth), seed=int(seed), max_rows=int(n), models=tuple(models)))
+
+    def mlp_utility(self, train_real, test_real=None, n: int = 40000, where=None, hidden: int = 100,
+                    steps: int = 1000, batch: int = 512, seed: int = 0, max_passes: int = 64) -> dict:
+        """MLP utility of n generated rows (eval/mlp_device.py): a network of one hidden layer of ``hidden`` units is
+        trained on them on the engine's device by ``steps`` Adam steps over strided batches of ``batch`` rows and
+        tested on real rows; ``mlp_f1_fake`` / ``mlp_acc_fake`` against ``mlp_f1_real`` / ``mlp_acc_real`` of the
+        same fit on ``train_real``, their gaps, and ``mlp_loss_fake`` of the fit.  Tables and the held-out default as
+        for :meth:`utility`.  The evaluator is kept per tables, n, hidden, steps, batch and seed."""
+        return self._mlp_evaluator(train_real, test_real, n, hidden, steps, batch, seed).score(
+            self.device_table(n, where=where, max_passes=max_passes)).floats()
+
+    def _mlp_evaluator(self, train_real, test_real, n: int, hidden: int = 100, steps: int = 1000, batch: int = 512,
+                       seed: int = 0):
+        from ..eval.mlp_device import DeviceMLP
+        params = (int(n), int(hidden), int(steps), int(batch), int(seed))
+        return self._cached("mlp", (train_real, test_real), params, lambda train, test: DeviceMLP(
+            *self._held_out(train, test), self.meta, self.vocabs, self.engine.device, ops=self.engine.ops,
+            hidden=int(hidden), steps=int(steps), batch=int(batch), seed=int(seed), max_rows=int(n)))
 
     def correlation(self, real, n: int = 40000, where=None, max_passes: int = 64) -> dict:
         """Diff. Corr. of n generated rows against ``real`` (a DataFrame or a CSV path): generated and scored on the

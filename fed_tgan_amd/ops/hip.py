@@ -740,6 +740,25 @@ class HipOps:
         """Same contract as TorchOps.util_predict."""
         self.L.util_predict(*self._util_table(tab, n), train_counts, W, conf, G, loss, real, out)
 
+    # ------------------------------------------------------------------ MLP-utility evaluator (kernels/mlp.hip)
+    MLP_MAX_HIDDEN = 128         # kernels/launch.h: H, a block's h [64, H] in LDS
+    MLP_MAX_BATCH = 1024         # rows of a batch
+    MLP_MAX_STEPS = 10000        # steps of a fit: two graph nodes each
+    MLP_ROWS = 64                # rows of a block (mlp_loss keeps one partial sum per block)
+
+    def mlp_step(self, tab, n, b, nb, theta, m, v, h, dz, dh, cnt, H, alpha, lr_t):
+        """Same contract as TorchOps.mlp_step."""
+        self.L.mlp_step(*self._util_table(tab, n), int(tab.D), int(b), int(nb), theta, m, v, h, dz, dh, cnt, int(H),
+                        float(alpha), float(lr_t))
+
+    def mlp_loss(self, tab, n, theta, H, alpha, loss):
+        """Same contract as TorchOps.mlp_loss."""
+        self.L.mlp_loss(*self._util_table(tab, n), int(tab.D), theta, int(H), float(alpha), loss)
+
+    def mlp_predict(self, tab, n, train_counts, theta, H, conf, loss, real, out):
+        """Same contract as TorchOps.mlp_predict."""
+        self.L.mlp_predict(*self._util_table(tab, n), int(tab.D), train_counts, theta, int(H), conf, loss, real, out)
+
     # ------------------------------------------------------------------ tree-utility evaluator (kernels/forest.hip)
     TREE_CONT, TREE_CAT, TREE_TARGET = 0, 1, 2
     TREE_MAX_BINS = 256          # kernels/launch.h: a bin is one byte

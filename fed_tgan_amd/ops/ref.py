@@ -879,14 +879,18 @@ class TorchOps:
         logit over the classes with train_counts > 0 (the lowest such class on a tie), rows whose target is no code
         skipped.  out[0..7] = weighted F1, accuracy, real[0], real[1], real[0] - F1, real[1] - accuracy, loss[0],
         max |G|."""
-        K = tab.K
         Z = self._util_logits(tab, n, W, self._util_codes(tab, n))
+        self._predict_conf(Z, train_counts, tab.y[:n].long(), tab.K, conf, real, out)
+        out[6], out[7] = loss[0], G.abs().max()
+
+    @staticmethod
+    def _predict_conf(Z, train_counts, y, K, conf, real, out):
+        """conf and out[0..5] of util_predict / mlp_predict from the logits Z [n, K] and the target codes y"""
         pres = (train_counts > 0)[None, :]
         Zm = torch.where(pres, Z, torch.full_like(Z, float("-inf")))
         mx = Zm.max(dim=1).values
         idx = torch.arange(K, device=Z.device)[None, :].expand_as(Z)
         pred = torch.where(Zm == mx[:, None], idx, torch.full_like(idx, K)).min(dim=1).values.clamp(max=K - 1)
-        y = tab.y[:n].long()
         ok = (y >= 0) & (y < K)
         c = torch.bincount(y[ok] * K + pred[ok], minlength=K * K).view(K, K)
         conf.copy_(c.to(conf.dtype).view(conf.shape))
@@ -899,7 +903,95 @@ class TorchOps:
         f1 = torch.where(total > 0, (rs * f).sum() / safe, torch.zeros_like(total))
         acc = torch.where(total > 0, tp.sum() / safe, torch.zeros_like(total))
         out[0], out[1], out[2], out[3] = f1, acc, real[0], real[1]
-        out[4], out[5], out[6], out[7] = real[0] - f1, real[1] - acc, loss[0], G.abs().max()
+        out[4], out[5] = real[0] - f1, real[1] - acc
+
+    # ------------------------------------------------------------------ MLP-utility evaluator (eval/mlp_device.py)
+    MLP_MAX_HIDDEN, MLP_MAX_BATCH, MLP_MAX_STEPS, MLP_ROWS = 128, 1024, 10000, 64    # the HIP kernels' limits
+
+    def _mlp_forward(self, tab, idx, theta, H):
+        """(W1, W2, codes, h, z) of the rows idx of a packed table: h = relu(F W1), z = [h | 1] W2, the one-hot part
+        of F W1 as the rows of W1 that the clamped codes select"""
+        D, K, nc, ol = tab.D, tab.K, tab.cont.shape[1], tab.offs.tolist()
+        W1, W2 = theta[:D * H].view(D, H), theta[D * H:D * H + (H + 1) * K].view(H + 1, K)
+        codes = [tab.cat_t[c].long()[idx].clamp(0, Kc) for c, Kc in enumerate(tab.card.tolist())]
+        pre = tab.cont[idx] @ W1[:nc]
+        for c, code in enumerate(codes):
+            pre = pre + W1[nc + ol[c] + code]
+        h = torch.clamp(pre + W1[D - 1][None, :], min=0.0)
+        return W1, W2, codes, h, h @ W2[:H] + W2[H][None, :]
+
+    @staticmethod
+    def _mlp_softmax(Z, y, counts, K):
+        """(valid rows, P - Y with zero rows where y is no code, the rows' cross entropies): the softmax runs over the
+        classes with counts > 0, the others get probability 0"""
+        pres = (counts > 0)[None, :]
+        mx = torch.where(pres, Z, torch.full_like(Z, float("-inf"))).max(dim=1).values
+        mx = torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))
+        E = torch.where(pres, torch.exp(Z - mx[:, None]), torch.zeros_like(Z))
+        den = E.sum(dim=1)
+        den = torch.where(den > 0, den, torch.ones_like(den))
+        valid = (y >= 0) & (y < K)
+        yv = y.clamp(0, K - 1)
+        Y = torch.zeros_like(Z).scatter_(1, yv[:, None], 1.0)
+        dZ = torch.where(valid[:, None], E / den[:, None] - Y, torch.zeros_like(Z))
+        ce = torch.log(den) + mx - Z.gather(1, yv[:, None])[:, 0]
+        return valid, dZ, torch.where(valid, ce, torch.zeros_like(ce))
+
+    def mlp_step(self, tab, n, b, nb, theta, m, v, h, dz, dh, cnt, H, alpha, lr_t):
+        """One Adam step of the network theta = [W1 [D, H] | W2 [H + 1, K]] (the last rows the biases) on batch b of
+        nb of the packed table ``tab``: its rows b, b + nb, ... < n.  g = grad of (sum over the batch's valid rows of
+        CE(softmax([relu(F W1) | 1] W2), y) + alpha / 2 |W1, W2 without their bias rows|^2) / max(valid rows, 1); m
+        = 0.9 m + 0.1 g, v = 0.999 v + 0.001 g^2, theta -= lr_t m / (sqrt(v) + 1e-8).  Scratch: h / dh float64
+        [>= rows H], dz float64 [>= rows K] (the batch's h, dH and dZ) and cnt int32 [>= ceil(rows / MLP_ROWS)] (valid
+        rows per block of MLP_ROWS batch rows)."""
+        D, K, nc = tab.D, tab.K, tab.cont.shape[1]
+        cl, ol = tab.card.tolist(), tab.offs.tolist()
+        idx = torch.arange(int(b), int(n), int(nb), device=theta.device)
+        rows = int(idx.numel())
+        if not 0 <= int(b) < int(nb) <= int(n) or rows > self.MLP_MAX_BATCH:
+            raise ValueError(f"mlp_step: batch {b} of {nb} over {n} rows has {rows} rows; MLP_MAX_BATCH = "
+                             f"{self.MLP_MAX_BATCH}")
+        W1, W2, codes, hh, Z = self._mlp_forward(tab, idx, theta, H)
+        valid, dZ, _ = self._mlp_softmax(Z, tab.y.long()[idx], tab.counts, K)
+        dH = (dZ @ W2[:H].t()) * (hh > 0).to(dZ.dtype)
+        g1 = torch.zeros(D, H, dtype=torch.float64, device=theta.device)
+        g1[:nc] = tab.cont[idx].t() @ dH
+        g1[D - 1] = dH.sum(dim=0)
+        for c, code in enumerate(codes):
+            g1[nc + ol[c]:nc + ol[c] + cl[c] + 1] = torch.zeros(cl[c] + 1, H, dtype=torch.float64,
+                                                               device=theta.device).index_add_(0, code, dH)
+        g1[:D - 1] += alpha * W1[:D - 1]
+        g2 = torch.cat([hh.t() @ dZ + alpha * W2[:H], dZ.sum(dim=0)[None, :]], dim=0)
+        nv = valid.sum()
+        g = torch.cat([g1.reshape(-1), g2.reshape(-1)]) / nv.clamp(min=1).to(torch.float64)
+        blocks = (rows + self.MLP_ROWS - 1) // self.MLP_ROWS
+        pad = torch.zeros(blocks * self.MLP_ROWS, dtype=torch.int64, device=theta.device)
+        pad[:rows] = valid.long()
+        cnt[:blocks] = pad.view(blocks, self.MLP_ROWS).sum(dim=1).to(cnt.dtype)
+        h.view(-1)[:rows * H] = hh.reshape(-1)
+        dh.view(-1)[:rows * H] = dH.reshape(-1)
+        dz.view(-1)[:rows * K] = dZ.reshape(-1)
+        m.mul_(0.9).add_(0.1 * g)
+        v.mul_(0.999).add_(0.001 * g * g)
+        theta.sub_(float(lr_t) * m / (torch.sqrt(v) + 1e-8))
+
+    def mlp_loss(self, tab, n, theta, H, alpha, loss):
+        """loss[0] = the objective of mlp_step over all n rows of ``tab`` (divided by its valid rows, 1 when there is
+        none).  loss: float64 [>= 1 + ceil(n / MLP_ROWS)]; what follows loss[0] is scratch of the HIP kernels."""
+        D, K = tab.D, tab.K
+        idx = torch.arange(int(n), device=theta.device)
+        W1, W2, _, _, Z = self._mlp_forward(tab, idx, theta, H)
+        valid, _, ce = self._mlp_softmax(Z, tab.y.long()[idx], tab.counts, K)
+        l2 = (W1[:D - 1] * W1[:D - 1]).sum() + (W2[:H] * W2[:H]).sum()
+        loss[0] = (ce.sum() + 0.5 * alpha * l2) / valid.sum().clamp(min=1).to(torch.float64)
+
+    def mlp_predict(self, tab, n, train_counts, theta, H, conf, loss, real, out):
+        """conf [K, K] int32 as util_predict's, from the network's logits; out[0..6] = weighted F1, accuracy, real[0],
+        real[1], real[0] - F1, real[1] - accuracy, loss[0]."""
+        idx = torch.arange(int(n), device=theta.device)
+        Z = self._mlp_forward(tab, idx, theta, H)[4]
+        self._predict_conf(Z, train_counts, tab.y[:n].long(), tab.K, conf, real, out)
+        out[6] = loss[0]
 
     # ------------------------------------------------------------------ tree-utility evaluator (eval/forest_device.py)
     TREE_CONT, TREE_CAT, TREE_TARGET = 0, 1, 2
