@@ -1088,8 +1088,9 @@ void cond_request(const Tensor& drive, const Tensor& bin_opt, const Tensor& bin_
 void cond_partition(const Tensor& drive, const Tensor& bin_opt, const Tensor& bin_code, const Tensor& quota,
                     const Tensor& filled, const Tensor& seg_off, const Tensor& fixed_j, const Tensor& fixed_code,
                     const Tensor& stats, const Tensor& out, const Tensor& tgt, const Tensor& dst, const Tensor& keep,
-                    const Tensor& counts) {
+                    const Tensor& counts, bool any_value) {
   fedtgan::CondPartitionArgs a{};
+  a.any_value = any_value ? 1 : 0;
   a.req = cond_req(drive, bin_opt, bin_code, quota, filled, seg_off, fixed_j, fixed_code, stats);
   TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kDouble && out.is_contiguous() && out.dim() == 2,
               "cond_partition: out must be contiguous float64 [rows, n_cols]");
@@ -1263,6 +1264,48 @@ void nn_top2(const Tensor& q_cont, const Tensor& q_cat, const Tensor& r_cont, co
   a.exclude_self = exclude_self ? 1 : 0;
   fedtgan::launch_nn_top2(a, d1.data_ptr<double>(), d2.data_ptr<double>(), i1.data_ptr<int>(),
                           scratch.data_ptr<double>(), cur_stream());
+}
+
+void nn_within(const Tensor& q_cont, const Tensor& q_cat, const Tensor& r_cont, const Tensor& r_cat, const Tensor& t2,
+               const Tensor& near, const Tensor& scratch) {
+  TORCH_CHECK(sim_f64(q_cont) && q_cont.dim() == 2 && sim_i32(q_cat) && q_cat.dim() == 2 &&
+                  q_cat.size(0) == q_cont.size(0), "nn_within: queries float64 [nq, n_cont] and int32 [nq, n_cat]");
+  TORCH_CHECK(sim_f64(r_cont) && r_cont.dim() == 2 && sim_i32(r_cat) && r_cat.dim() == 2 &&
+                  r_cat.size(0) == r_cont.size(0) && r_cont.size(1) == q_cont.size(1) &&
+                  r_cat.size(1) == q_cat.size(1), "nn_within: reference rows with the queries' columns");
+  const int64_t nq = q_cont.size(0), nr = r_cont.size(0);
+  TORCH_CHECK(nr >= 1 && nr < (int64_t)INT32_MAX && nq < (int64_t)INT32_MAX && q_cont.size(1) + q_cat.size(1) >= 1,
+              "nn_within: at least one reference row and one column");
+  TORCH_CHECK(sim_f64(t2) && t2.numel() == 1, "nn_within: t2 is one float64 on the device");
+  TORCH_CHECK(sim_i32(near) && near.numel() >= nq, "nn_within: near int32, one entry per query");
+  // (the partials are int32: two to a float64 of the scratch nn_top2 uses)
+  const int64_t slots = nq * fedtgan::nn_chunks(nr);
+  TORCH_CHECK(sim_f64(scratch) && 2 * scratch.numel() >= slots, "nn_within: scratch needs ", (slots + 1) / 2,
+              " float64");
+  if (nq == 0) return;
+  fedtgan::NnWithinArgs a{};
+  a.nq = (int)nq;
+  a.nr = (int)nr;
+  a.n_cont = (int)q_cont.size(1);
+  a.n_cat = (int)q_cat.size(1);
+  a.q_cont = a.n_cont ? q_cont.data_ptr<double>() : nullptr;
+  a.r_cont = a.n_cont ? r_cont.data_ptr<double>() : nullptr;
+  a.q_cat = a.n_cat ? q_cat.data_ptr<int>() : nullptr;
+  a.r_cat = a.n_cat ? r_cat.data_ptr<int>() : nullptr;
+  a.t2 = t2.data_ptr<double>();
+  a.near = near.data_ptr<int>();
+  a.part = (int*)scratch.data_ptr<double>();
+  fedtgan::launch_nn_within(a, cur_stream());
+}
+
+void guard_mark(const Tensor& near, const Tensor& tgt, const Tensor& stats) {
+  const int64_t n = tgt.numel();
+  TORCH_CHECK(sim_i32(near) && sim_i32(tgt) && near.numel() >= n && n < (int64_t)INT32_MAX,
+              "guard_mark: near / tgt int32, one entry per row");
+  TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kLong && stats.is_contiguous() && stats.numel() == 2,
+              "guard_mark: stats int64 [2]");
+  fedtgan::launch_guard_mark(near.data_ptr<int>(), tgt.data_ptr<int>(), (int)n, stats.data_ptr<int64_t>(),
+                             cur_stream());
 }
 
 void nn_stats(const Tensor& d1, const Tensor& d2, int64_t n, const Tensor& keys, const Tensor& part) {
@@ -2238,7 +2281,7 @@ TORCH_LIBRARY(fedtgan, m) {
   m.def(
       "cond_partition(Tensor drive, Tensor bin_opt, Tensor bin_code, Tensor quota, Tensor(a!) filled, Tensor seg_off, "
       "Tensor fixed_j, Tensor fixed_code, Tensor(b!) stats, Tensor out, Tensor tgt, Tensor(c!) dst, Tensor(d!) keep, "
-      "Tensor(e!) counts) -> ()");
+      "Tensor(e!) counts, bool any_value=False) -> ()");
   m.def("cond_partition_workgroups(int rows) -> int", &cond_partition_workgroups);
   m.def(
       "sim_prepare(Tensor values, Tensor kind, Tensor slot, Tensor vocab, Tensor(a!) keys, Tensor(b!) valid, "
@@ -2256,6 +2299,10 @@ TORCH_LIBRARY(fedtgan, m) {
   m.def(
       "nn_top2(Tensor q_cont, Tensor q_cat, Tensor r_cont, Tensor r_cat, bool exclude_self, Tensor(a!) d1, "
       "Tensor(b!) d2, Tensor(c!) i1, Tensor(d!) scratch) -> ()");
+  m.def(
+      "nn_within(Tensor q_cont, Tensor q_cat, Tensor r_cont, Tensor r_cat, Tensor t2, Tensor(a!) near, "
+      "Tensor(b!) scratch) -> ()");
+  m.def("guard_mark(Tensor near, Tensor(a!) tgt, Tensor(b!) stats) -> ()");
   m.def("nn_stats(Tensor d1, Tensor d2, int n, Tensor(a!) keys, Tensor(b!) part) -> ()");
   m.def("nn_percentiles(Tensor keys, int n, Tensor part, Tensor(a!) out) -> ()");
   m.def("nn_query_tile() -> int", &nn_query_tile);
@@ -2380,6 +2427,8 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("sim_mean", &sim_mean);
   m.impl("nn_pack", &nn_pack);
   m.impl("nn_top2", &nn_top2);
+  m.impl("nn_within", &nn_within);
+  m.impl("guard_mark", &guard_mark);
   m.impl("nn_stats", &nn_stats);
   m.impl("nn_percentiles", &nn_percentiles);
   m.impl("corr_pack", &corr_pack);

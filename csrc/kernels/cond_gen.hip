@@ -117,7 +117,7 @@ __global__ __launch_bounds__(COND_THREADS) void cond_flag_kernel(CondPartitionAr
 #if FT_CHECKED
     FT_CHECK(&g_check_cond, t >= -1 && t < a.req.n_bins, CHK_COND_REQUEST);
 #endif
-    if (keep) {
+    if (keep && !a.any_value) {
       const double* row = a.out + (size_t)r * a.n_cols;
       const int dj = a.req.drive[1];
       keep = dj >= 0 && dj < a.n_cols && row[dj] == a.req.bin_code[t];

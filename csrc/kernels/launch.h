@@ -451,6 +451,8 @@ struct CondPartitionArgs {
   int* counts;               // [cond_partition_workgroups(rows), n_bins] scratch: kept rows per workgroup and bin
   double* dst;               // [n_dst, n_cols] the quota segments
   int64_t n_dst;
+  int any_value;             // off by default; on: no value predicate, a row with a target is kept (the privacy guard
+                             // without a request: one bin, drive / bin_code / fixed_* unread)
 };
 int cond_partition_workgroups(int rows);
 void launch_cond_partition(const CondPartitionArgs& a, hipStream_t stream);
@@ -536,6 +538,21 @@ int64_t nn_scratch_doubles(int64_t nq, int64_t nr);   // fp64 elements of scratc
 // per query: d1 <= d2 the two smallest d2 over the candidates (with multiplicity; +inf where there are fewer) and
 // i1 the lowest index at distance d1 (-1: no candidate)
 void launch_nn_top2(NnTop2Args a, double* d1, double* d2, int* i1, double* scratch, hipStream_t stream);
+struct NnWithinArgs {
+  const double* q_cont;   // [nq, n_cont]
+  const int* q_cat;       // [nq, n_cat]
+  const double* r_cont;   // [nr, n_cont]
+  const int* r_cat;       // [nr, n_cat]
+  int nq, nr, n_cont, n_cat;
+  const double* t2;       // [1] on the device: the squared radius (one captured launch serves every threshold)
+  int* near;              // [nq] lowest index of a reference row with d2 <= t2, or -1
+  int* part;              // [nn_chunks(nr), nq] scratch: the per-chunk answers
+  int chunks;             // set by the launcher
+};
+// the radius test of the privacy guard: d2 as launch_nn_top2 computes it, candidates abandoned once out of range
+void launch_nn_within(NnWithinArgs a, hipStream_t stream);
+// tgt[i] = -1 where near[i] >= 0; stats[0] += n, stats[1] += rows with near >= 0
+void launch_guard_mark(const int* near, int* tgt, int n, int64_t* stats, hipStream_t stream);
 int nn_stats_blocks(int64_t n);
 // keys [2, ld]: sqrt(d1) and the ratio sqrt(d1 / d2) of rows [0, n); part [2 * nn_stats_blocks(n)]
 void launch_nn_stats(const double* d1, const double* d2, int n, double* keys, int64_t ld, double* part,

@@ -6,6 +6,9 @@
 //                         registers), the workgroup shares a tile of NN_REF_TILE reference rows staged in LDS, and every
 //                         (query, chunk) pair leaves its partial (d1, d2, i1) in scratch
 //  nn_merge_kernel        the partials of a query folded in chunk order (strict <: the lowest index wins a tie)
+//  nn_within_kernel       the privacy guard's radius test on the same grid: the lowest reference row with d2 <= t2 per
+//                         (query, chunk), candidates abandoned once out of range; nn_within_merge_kernel takes the
+//                         first chunk with a hit, guard_mark_kernel clears the target of the rows that have one
 //  nn_stats_kernel        sqrt(d1) and the distance ratio into two key rows (sorted by launch_sim_sort afterwards);
 //                         per-workgroup minimum and count of exact zeros in fixed slots
 //  nn_percentile_kernel   the two interpolated 5th percentiles from the sorted rows, the minimum and the share of zeros
@@ -216,6 +219,216 @@ void launch_nn_top2(NnTop2Args a, double* d1, double* d2, int* i1, double* scrat
   const unsigned tiles = (unsigned)((a.nq + NN_QUERY_TILE - 1) / NN_QUERY_TILE);
   hipLaunchKernelGGL(nn_top2_kernel, dim3(tiles, (unsigned)a.chunks), dim3(NN_THREADS), 0, stream, a);
   hipLaunchKernelGGL(nn_merge_kernel, dim3(tiles), dim3(NN_THREADS), 0, stream, a, d1, d2, i1);
+}
+
+// ============================================================================ radius test (the privacy guard)
+// near[q] = the lowest index of a reference row with d2(q, r) <= t2, or -1: nn_top2's grid, tiles and column blocks,
+// but no candidate needs an exact distance once it is out of range, and no query a second neighbour.
+//
+//  (1) a tile's categorical mismatches are counted first (all column blocks).  They are integers, and every
+//      continuous term is >= 0, so a candidate with (double)cnt > t2 is dead, also while its count is still partial: a
+//      wave whose candidates are all dead stops counting.  Where no thread of the workgroup has a candidate left,
+//      the tile's continuous columns are not staged at all.
+//  (2) the continuous columns add up as in nn_top2_kernel (column order, acc = fma(d, d, acc): the instruction the
+//      compiler contracts nn_top2's `acc += d * d` to), NN_WITHIN_GROUP columns at a time; after a group a candidate
+//      with acc + (double)cnt > t2 is dead.  That is exact: fp64 rounding is monotone and every term is >= 0, so the
+//      final acc is no smaller than a partial one, and neither is the final acc + (double)cnt.  A wave without a
+//      candidate left skips the block's remaining groups.
+//  (3) candidates are visited in ascending index order, so the first hit of a chunk is its lowest: a query with a hit
+//      has no candidates in later tiles, and a workgroup whose live queries all have hits leaves the chunk.
+//
+// A surviving candidate's distance is the very acc + (double)cnt nn_top2 computes, so a row this test keeps is a row
+// the evaluator scores at d1 > t2.  A NaN distance never compares > t2, is never pruned and never hits.
+constexpr int NN_WITHIN_GROUP = 4;
+constexpr unsigned NN_TILE_MASK = (1u << NN_REF_TILE) - 1u;
+constexpr int NN_CAT_PER_THREAD = (NN_REF_TILE * NN_QK + NN_THREADS - 1) / NN_THREADS;   // staged codes per thread
+
+__global__ __launch_bounds__(NN_THREADS) void nn_within_kernel(NnWithinArgs a) {
+  __shared__ __attribute__((aligned(16))) double sc[NN_QC][NN_PAD_C];
+  __shared__ __attribute__((aligned(16))) int sk[NN_QK][NN_PAD_K];
+  const int tid = threadIdx.x;
+  const int q = blockIdx.x * NN_QUERY_TILE + tid;
+  const bool live = q < a.nq;
+  const int chunk = blockIdx.y;
+  const int j0 = chunk * NN_CHUNK_ROWS;
+  const int j1 = min(a.nr, j0 + NN_CHUNK_ROWS);
+  const int nbc = (a.n_cont + NN_QC - 1) / NN_QC, nbk = (a.n_cat + NN_QK - 1) / NN_QK;
+  const double* qc = a.q_cont + (size_t)(live ? q : 0) * a.n_cont;
+  const int* qk = a.q_cat + (size_t)(live ? q : 0) * a.n_cat;
+  const double t2 = *a.t2;
+  // (double)cnt > t2 exactly when cnt > kmax, for every int cnt >= 0 (t2 = NaN: never, as the comparison)
+  const int kmax = !(t2 < 2147483647.0) ? 2147483647 : (t2 < 0.0 ? -1 : (int)floor(t2));
+
+  double qv[NN_QC];
+  int qi[NN_QK];
+  auto load_cont = [&](int b) {
+#pragma unroll
+    for (int c = 0; c < NN_QC; ++c) {
+      const int col = b * NN_QC + c;
+      qv[c] = col < a.n_cont ? qc[col] : 0.0;
+    }
+  };
+  auto load_cat = [&](int b) {
+#pragma unroll
+    for (int c = 0; c < NN_QK; ++c) {
+      const int col = b * NN_QK + c;
+      qi[c] = col < a.n_cat ? qk[col] : 0;
+    }
+  };
+  load_cont(0);
+  load_cat(0);
+  // this thread's share of a staged block of codes (rows past the chunk and columns past the table: 0, not read)
+  int pre[NN_CAT_PER_THREAD];
+  auto fetch_cat = [&](int jt, int b) {
+#pragma unroll
+    for (int i = 0; i < NN_CAT_PER_THREAD; ++i) {
+      const int e = tid + i * NN_THREADS;
+      const int r = e / NN_QK, c = e - r * NN_QK;
+      const int j = jt + r, col = b * NN_QK + c;
+      pre[i] = (r < NN_REF_TILE && j < j1 && col < a.n_cat) ? a.r_cat[(size_t)j * a.n_cat + col] : 0;
+    }
+  };
+  fetch_cat(j0, 0);
+
+  int hit = -1;
+  for (int jt = j0; jt < j1; jt += NN_REF_TILE) {
+    // (3) also the barrier after which the previous tile's LDS may be overwritten
+    if (__syncthreads_and(!live || hit >= 0)) break;
+    const int left = j1 - jt;                                // rows of this tile that exist
+    unsigned alive = (live && hit < 0) ? (left >= NN_REF_TILE ? NN_TILE_MASK : (1u << left) - 1u) : 0u;
+    int cnt[NN_REF_TILE];
+#pragma unroll
+    for (int r = 0; r < NN_REF_TILE; ++r) cnt[r] = 0;
+    // (1) mismatch counts of every categorical block, NN_WITHIN_GROUP columns at a time: once the smallest count of
+    // every query of the wave is past kmax all its candidates are dead, and counting them further changes nothing
+    bool counting = __any(alive != 0u);                       // (uniform over the wave)
+    for (int b = 0; b < nbk; ++b) {
+      const int nkb = min(NN_QK, a.n_cat - b * NN_QK);
+      if (b > 0) __syncthreads();
+      if (nbk > 1) load_cat(b);
+      // the codes fetched while the previous block / tile was counted go to LDS; the next ones are requested now, so
+      // their latency hides behind this block's counting (a pruned tile is little else than this staging)
+#pragma unroll
+      for (int i = 0; i < NN_CAT_PER_THREAD; ++i) {
+        const int e = tid + i * NN_THREADS;
+        if (e < NN_REF_TILE * NN_QK) sk[e % NN_QK][e / NN_QK] = pre[i];
+      }
+      if (b + 1 < nbk) fetch_cat(jt, b + 1);
+      else fetch_cat(jt + NN_REF_TILE, 0);
+      __syncthreads();
+#pragma unroll
+      for (int g = 0; g < NN_QK; g += NN_WITHIN_GROUP) {
+        if (g < nkb && counting) {                            // (no barrier inside)
+#pragma unroll
+          for (int c = g; c < g + NN_WITHIN_GROUP; ++c) {
+            if (c < nkb) {                                    // (uniform over the workgroup)
+              const int x = qi[c];
+#pragma unroll
+              for (int r = 0; r < NN_REF_TILE; ++r) cnt[r] += (x != sk[c][r]) ? 1 : 0;
+            }
+          }
+          int least = cnt[0];
+#pragma unroll
+          for (int r = 1; r < NN_REF_TILE; ++r) least = min(least, cnt[r]);
+          counting = __any(alive != 0u && least <= kmax);
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < NN_REF_TILE; ++r)
+      if (cnt[r] > kmax) alive &= ~(1u << r);
+    if (nbc > 0) {
+      if (!__syncthreads_or(alive != 0u)) continue;          // the whole tile is dead for this workgroup
+    }
+    double acc[NN_REF_TILE];
+#pragma unroll
+    for (int r = 0; r < NN_REF_TILE; ++r) acc[r] = 0.0;
+    // (2) continuous columns in column order
+    for (int b = 0; b < nbc; ++b) {
+      const int ncb = min(NN_QC, a.n_cont - b * NN_QC);
+      if (b > 0) __syncthreads();
+      if (nbc > 1) load_cont(b);
+      for (int e = tid; e < NN_REF_TILE * NN_QC; e += NN_THREADS) {
+        const int r = e / NN_QC, c = e - r * NN_QC;
+        const int j = jt + r, col = b * NN_QC + c;
+        sc[c][r] = (j < j1 && col < a.n_cont) ? a.r_cont[(size_t)j * a.n_cont + col] : 0.0;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int g = 0; g < NN_QC; g += NN_WITHIN_GROUP) {
+        if (g < ncb && __any(alive != 0u)) {                  // (uniform over the wave; no barrier inside)
+#pragma unroll
+          for (int c = g; c < g + NN_WITHIN_GROUP; ++c) {
+            if (c < ncb) {
+              const double x = qv[c];
+#pragma unroll
+              for (int r = 0; r < NN_REF_TILE; ++r) {
+                const double d = x - sc[c][r];
+                acc[r] = fma(d, d, acc[r]);
+              }
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < NN_REF_TILE; ++r)
+            if (acc[r] + (double)cnt[r] > t2) alive &= ~(1u << r);
+        }
+      }
+    }
+    // a candidate still alive went through every column: its distance is complete
+#pragma unroll
+    for (int r = NN_REF_TILE - 1; r >= 0; --r)
+      if (((alive >> r) & 1u) && acc[r] + (double)cnt[r] <= t2) hit = jt + r;
+  }
+  if (live) a.part[(size_t)chunk * a.nq + q] = hit;
+}
+
+// chunk c holds indices below chunk c + 1's: the first chunk with a hit has the lowest
+__global__ __launch_bounds__(NN_THREADS) void nn_within_merge_kernel(NnWithinArgs a) {
+  const int q = blockIdx.x * NN_THREADS + threadIdx.x;
+  if (q >= a.nq) return;
+  int hit = -1;
+  for (int c = 0; c < a.chunks && hit < 0; ++c) hit = a.part[(size_t)c * a.nq + q];
+  a.near[q] = hit;
+}
+
+void launch_nn_within(NnWithinArgs a, hipStream_t stream) {
+  require_unbatched("nn_within");
+  if (a.nq < 0 || a.nr < 1 || a.n_cont < 0 || a.n_cat < 0 || a.n_cont + a.n_cat < 1)
+    throw std::runtime_error("nn_within: table sizes");
+  if (a.nq == 0) return;
+  a.chunks = nn_chunks(a.nr);
+  if (a.chunks > 65535) throw std::runtime_error("nn_within: too many reference rows");
+  const unsigned tiles = (unsigned)((a.nq + NN_QUERY_TILE - 1) / NN_QUERY_TILE);
+  hipLaunchKernelGGL(nn_within_kernel, dim3(tiles, (unsigned)a.chunks), dim3(NN_THREADS), 0, stream, a);
+  hipLaunchKernelGGL(nn_within_merge_kernel, dim3(tiles), dim3(NN_THREADS), 0, stream, a);
+}
+
+// tgt[i] = -1 where near[i] >= 0 (cond_flag_kernel keeps no such row); stats += [rows, rows with a hit], counted
+// with ballots and integer atomics, so the sums do not depend on the order the workgroups run in
+__global__ __launch_bounds__(NN_THREADS) void guard_mark_kernel(const int* near, int* tgt, int n,
+                                                                unsigned long long* stats) {
+  __shared__ int wsum[NN_THREADS / WAVE];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * NN_THREADS + tid;
+  const bool rej = i < n && near[i] >= 0;
+  if (rej) tgt[i] = -1;
+  const unsigned long long b = __ballot(rej);
+  if ((tid & (WAVE - 1)) == 0) wsum[tid / WAVE] = __popcll(b);
+  __syncthreads();
+  if (tid == 0) {
+    int s = 0;
+    for (int w = 0; w < NN_THREADS / WAVE; ++w) s += wsum[w];
+    if (s) atomicAdd(&stats[1], (unsigned long long)s);
+    if (blockIdx.x == 0) atomicAdd(&stats[0], (unsigned long long)n);
+  }
+}
+
+void launch_guard_mark(const int* near, int* tgt, int n, int64_t* stats, hipStream_t stream) {
+  require_unbatched("guard_mark");
+  if (n < 0) throw std::runtime_error("guard_mark: row count");
+  if (n == 0) return;
+  hipLaunchKernelGGL(guard_mark_kernel, dim3((unsigned)((n + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS), 0,
+                     stream, near, tgt, n, (unsigned long long*)stats);
 }
 
 // ============================================================================ table scores

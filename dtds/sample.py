@@ -28,6 +28,11 @@ def main(argv=None):
                    help="the same as JSON; one column may map values to weights, e.g. "
                         "'{\"class\": {\"back.\": 1, \"satan.\": 1}, \"protocol_type\": \"tcp\"}' (-n rows split by weight)")
     p.add_argument("-max_passes", type=int, default=64, help="generation passes a conditional request may take")
+    p.add_argument("-min_dcr", type=float, default=None, metavar="T",
+                   help="privacy guard: write only rows farther than T from every real record, in the metric of "
+                        "-privacy_against (0 keeps out exact copies); still exactly -n rows")
+    p.add_argument("-guard_against", default=None, metavar="REAL.csv",
+                   help="the real table of -min_dcr (default: the table of -privacy_against)")
     p.add_argument("-score_against", default=None, metavar="REAL.csv",
                    help="also print Avg_JSD / Avg_WD of the generated rows against this table, scored on the device")
     p.add_argument("-privacy_against", default=None, metavar="REAL.csv",
@@ -64,6 +69,13 @@ def main(argv=None):
     if (args.utility_hidden != 100 or args.utility_steps != 1000 or args.utility_batch != 512) and \
             not args.utility_against:
         p.error("-utility_hidden / -utility_steps / -utility_batch need -utility_against")
+    guard_real = args.guard_against or args.privacy_against
+    if args.min_dcr is not None and guard_real is None:
+        p.error("-min_dcr needs a real table: -guard_against or -privacy_against")
+    if args.min_dcr is not None and not (args.min_dcr >= 0 and args.min_dcr != float("inf")):
+        p.error("-min_dcr is a finite number >= 0")
+    if args.guard_against and args.min_dcr is None:
+        p.error("-guard_against needs -min_dcr")
     import torch
     from fed_tgan_amd.models.conditional import parse_where
     from fed_tgan_amd.models.generator_io import load_generator
@@ -79,13 +91,21 @@ def main(argv=None):
             corr_real=args.corr_against, where=where or None, max_passes=args.max_passes,
             utility_real=args.utility_against, utility_test=args.utility_test, utility_iters=args.utility_iters,
             utility_models=utility_models, utility_trees=args.utility_trees, utility_depth=args.utility_depth,
-            utility_hidden=args.utility_hidden, utility_steps=args.utility_steps, utility_batch=args.utility_batch)
+            utility_hidden=args.utility_hidden, utility_steps=args.utility_steps, utility_batch=args.utility_batch,
+            min_dcr=args.min_dcr, guard_real=guard_real if args.min_dcr is not None else None)
+    elif args.min_dcr is not None:
+        gen.write_csv(out, args.n, where=where or None, max_passes=args.max_passes, min_dcr=args.min_dcr,
+                      guard_real=guard_real)
     else:
         gen.write_csv(out, args.n, where=where or None, max_passes=args.max_passes)
     cond = ""
     if where:
         lc = gen.engine.last_conditional
         cond = f", {lc['passes']} passes, {lc['kept']} of {lc['generated']} generated rows accepted"
+    if args.min_dcr is not None:
+        lg = gen.engine.last_guard
+        cond += (f", guard min_dcr {args.min_dcr!r}: {lg['passes']} passes, {lg['rejected']} of {lg['generated']} "
+                 "generated rows rejected")
     print(f"{args.n} rows -> {out} ({time.time() - t0:.3f} s, {gen.engine.ops.name} on {dev}{cond})", flush=True)
     if scores is not None:
         print(f"Avg_JSD {scores[0]!r} Avg_WD {scores[1]!r} (against {args.score_against})", flush=True)

@@ -161,3 +161,76 @@ class DevicePrivacy(DeviceEvaluator):
         values are a precondition).  The work is queued on the current stream; the returned scores are device
         tensors and nothing waits for them."""
         return super().score(values)
+
+    def guard(self, min_dcr: float = 0.0) -> "PrivacyGuard":
+        """A :class:`PrivacyGuard` of radius ``min_dcr`` around this evaluator's real rows, sharing its packed table."""
+        return PrivacyGuard._sharing(self, min_dcr)
+
+
+def squared_radius(min_dcr) -> float:
+    """t2 = T * T, one float64 product on the host; T must be a finite number >= 0."""
+    t = float(min_dcr)
+    if not np.isfinite(t) or t < 0:
+        raise ValueError(f"min_dcr must be a finite number >= 0, got {min_dcr!r}")
+    return t * t
+
+
+class PrivacyGuard:
+    """Generate only rows farther than ``min_dcr`` from every real record (``CTGANEngine.generate_decoded_guarded``).
+
+    A generated row q is rejected iff some real row r has ``d2(q, r) <= t2`` with ``t2 = min_dcr * min_dcr`` and d2
+    exactly :class:`DevicePrivacy`'s, so ``min_dcr = 0`` rejects exact copies only, and a row the guard keeps is a
+    row the evaluator scores at ``d1 > t2``.  The guard holds what the evaluator holds -- the packed real table
+    ``r_cont`` / ``r_cat``, ``lo``, ``scale``, ``kind``, ``slot`` -- and ``t2`` as a one-element device tensor, and
+    refuses the same inputs (date tables, real values that are not finite).  The real records have to be on the
+    generating machine."""
+
+    def __init__(self, real, meta: dict, vocabs: Sequence, device, min_dcr: float = 0.0, ops=None):
+        t2 = squared_radius(min_dcr)            # (refused before the table is packed)
+        self._adopt(DevicePrivacy(real, meta, vocabs, device, ops=ops, max_rows=1, baseline=False), min_dcr, t2)
+
+    @classmethod
+    def _sharing(cls, evaluator: DevicePrivacy, min_dcr: float) -> "PrivacyGuard":
+        self = cls.__new__(cls)
+        self._adopt(evaluator, min_dcr, squared_radius(min_dcr))
+        return self
+
+    def _adopt(self, ev: DevicePrivacy, min_dcr: float, t2: float) -> None:
+        self.device, self.ops = ev.device, ev.ops
+        self.n_cols, self.n_cont, self.n_cat, self.n_real = ev.n_cols, ev.n_cont, ev.n_cat, ev.n_real
+        self.kind, self.slot, self.lo, self.scale = ev.kind, ev.slot, ev.lo, ev.scale
+        self.r_cont, self.r_cat = ev.r_cont, ev.r_cat
+        self.min_dcr = float(min_dcr)
+        self.t2 = torch.tensor([t2], dtype=torch.float64, device=self.device)
+
+    def buffers(self, rows: int):
+        """(q_cont, q_cat, near, scratch) for passes of up to ``rows`` rows"""
+        dev = self.device
+        return (torch.zeros(rows, self.n_cont, dtype=torch.float64, device=dev),
+                torch.zeros(rows, self.n_cat, dtype=torch.int32, device=dev),
+                torch.full((rows,), -1, dtype=torch.int32, device=dev),
+                torch.zeros(self.ops.nn_scratch(rows, self.n_real), dtype=torch.float64, device=dev))
+
+    def launch(self, values: torch.Tensor, q_cont, q_cat, near, scratch) -> None:
+        """nn_pack -> nn_within of a decoded pass over buffers from :meth:`buffers`; nothing is allocated."""
+        n = values.shape[0]
+        self.ops.nn_pack(values, self.kind, self.slot, self.lo, self.scale, q_cont, q_cat)
+        self.ops.nn_within(q_cont[:n], q_cat[:n], self.r_cont, self.r_cat, self.t2, near[:n], scratch)
+
+    def near(self, values: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """values: any [n, n_cols] float64 table on the guard's device -> (too close: bool [n], near: int32 [n], the
+        lowest index of a real row within the radius or -1)."""
+        if values.dim() != 2 or values.shape[1] != self.n_cols or values.dtype != torch.float64:
+            raise ValueError(f"near: expected a float64 [n, {self.n_cols}] table, got {tuple(values.shape)} "
+                             f"{values.dtype}")
+        if values.device != self.t2.device:
+            raise ValueError(f"near: the table is on {values.device}, the guard on {self.t2.device}")
+        n = int(values.shape[0])
+        bufs = self.buffers(max(n, 1))
+        if n:
+            self.launch(values.contiguous(), *bufs)
+        check = getattr(self.ops, "check", None)
+        if check is not None:
+            check()
+        near = bufs[2][:n]
+        return near >= 0, near

@@ -35,10 +35,12 @@ class GenerationMixin:
         self.gen_tables = self.gen_cond = None    # set_generation_tables
         # _gen_bufs: (H, logits, col, opt) of the eager passes, grown on demand; _gen_graphs / _gen_split: n -> the
         # captured generate_decoded(n) / prep + body of generate_decoded_split(n); _cond_ent: (m, bins, fixed
-        # columns) -> buffers / hipGraph of a conditional pass; _gen_prepped: event, the last pipelined prep is issued
+        # columns) -> buffers / hipGraph of a conditional pass, _guard_ent: the same of a guarded pass; _gen_prepped:
+        # event, the last pipelined prep is issued
         self._drop_generation()
         self._gen_done = None                     # event: the last pipelined generation body has finished
         self.last_conditional = None              # generate_decoded_where: passes, rows generated / kept, filled counts
+        self.last_guard = None                    # generate_decoded_guarded: passes, rows generated / rejected / kept
         self._gw16 = self._gwt = None             # bf16 / transposed generation copies of the generator weights
         self._gsnap = self._gsnap_pairs = self._gsnap_ctr = None      # pipelined generation: parameter / RNG snapshot
 
@@ -73,6 +75,7 @@ class GenerationMixin:
         self._gen_graphs: Dict[int, GenGraph] = {}
         self._gen_split: Dict[int, GenGraph] = {}
         self._cond_ent: Dict[tuple, dict] = {}
+        self._guard_ent: Dict[tuple, dict] = {}
         self._gen_bufs = self._gen_prepped = None
 
     def _prepare_generation_graphs(self, gen_rows: Sequence[int], gen_split: bool) -> None:
@@ -346,6 +349,166 @@ class GenerationMixin:
             req["filled"].zero_()
             req["stats"].zero_()
         run = partial(self._cond_pass, ent, m)
+        ent["graph"], = warm_and_capture(self.device, run, [run], snapshot=ctr.clone, restore=restore,
+                                         mode=self.capture_mode)
+
+    # ------------------------------------------------------------------ guarded generation
+    @torch.no_grad()
+    def generate_decoded_guarded(self, n: int, guard, request: dict | None = None, max_passes: int = 64,
+                                 chunk: int | None = None, use_graph: bool | None = None) -> torch.Tensor:
+        """Exactly n decoded rows none of which lies within the guard's radius of a real record: [n, n_cols] float64
+        on the device.  ``guard``: eval/privacy.py PrivacyGuard on this engine's device; a generated row q is
+        rejected iff some real row r has d2(q, r) <= guard.t2, with the privacy evaluator's d2.  Without ``request``
+        the rows come in generation order (pass, then row); with one (models/conditional.py build_request) the table
+        holds exactly the requested counts, grouped as generate_decoded_where groups them.
+
+        One pass over m rows (``chunk``, default as generate_decoded_where): sample_gen -> cond_request (only with a
+        request; else every row gets target 0) -> eval generator -> sample_decode -> nn_pack -> nn_within ->
+        guard_mark (a row within the radius loses its target) -> cond_partition (without a request: one bin, no
+        value compared).  Every row of every pass is tested.  Passes are issued in bursts with one readback per
+        burst, captured once per (m, bins, fixed columns, guard) and replayed as in generate_decoded_where, the RNG
+        counter and the counters restored after the warm-up, so eager and replayed runs from equal states give
+        bit-identical tables.  max_passes passes without n rows raise ConditionalSamplingError (no table; the message
+        carries the rejected share).  ``self.last_guard`` = {"passes", "generated", "rejected", "kept"}; with a
+        request ``self.last_conditional`` is set as generate_decoded_where sets it."""
+        from .conditional import ConditionalSamplingError
+        if self.gen_tables is None:
+            raise RuntimeError("set_generation_tables() first")
+        n = int(n)
+        n_cols = len(self.gen_tables["cols"])
+        if guard.n_cols != n_cols or guard.t2.device != self.flat.device:
+            raise ValueError(f"the guard holds {guard.n_cols}-column rows on {guard.t2.device}; the engine generates "
+                             f"{n_cols}-column rows on {self.flat.device}")
+        if request is not None:
+            quotas = [int(q) for q in request["quotas"]]
+            if n != int(request["n"]) or sum(quotas) != n:
+                raise ValueError(f"the request was built for {request['n']} rows, not {n}")
+            nb, nf, values = len(quotas), int(request["fixed_j"].numel()), list(request["values"])
+            if nb > getattr(self.ops, "COND_MAX_BINS", 64):
+                raise ValueError(f"{nb} requested values; the kernels' bin limit is {self.ops.COND_MAX_BINS}")
+        else:
+            if n < 0:
+                raise ValueError("n must be non-negative")
+            quotas, nb, nf, values = [n], 1, 0, []
+        if n == 0:
+            self.last_guard = {"passes": 0, "generated": 0, "rejected": 0, "kept": 0}
+            if request is not None:
+                self.last_conditional = {"passes": 0, "generated": 0, "kept": 0, "filled": [0] * nb, "values": values}
+            return self._decoded(0)
+        if use_graph is None:
+            use_graph = self._graphs_for_generation()
+        if chunk is not None:
+            m = int(chunk)
+            if m < 1:
+                raise ValueError("chunk must be positive")
+        else:
+            m = min(int(self.cfg.gen_chunk), max(1024, 1 << int(np.ceil(np.log2(max(1.25 * n, 1.0))))))
+        self._wait_gen_done()
+        ent = self._guard_entry(m, nb, nf, n, guard, request is not None)
+        req = ent["req"]
+        if request is not None:
+            for k in ("drive", "bin_opt", "bin_code", "quota", "seg_off", "fixed_j", "fixed_code"):
+                req[k].copy_(request[k])
+        else:
+            req["quota"].fill_(n)
+        req["filled"].zero_()
+        req["stats"].zero_()
+        ent["gstats"].zero_()
+        if use_graph and ent.get("graph") is None:
+            self._capture_guard(ent, m)
+
+        def report(passes, filled):
+            g = ent["gstats"].tolist()
+            self.last_guard = {"passes": int(passes), "generated": int(g[0]), "rejected": int(g[1]),
+                               "kept": int(sum(filled))}
+            if request is not None:
+                self.last_conditional = self._cond_report(ent, request, passes, filled)
+        passes, filled = 0, [0] * nb
+        while True:
+            open_rows = sum(q - f for q, f in zip(quotas, filled))
+            if open_rows <= 0:
+                break
+            if passes >= int(max_passes):
+                report(passes, filled)
+                if hasattr(self.ops, "check"):
+                    self.ops.check()
+                lg = self.last_guard
+                share = lg["rejected"] / max(lg["generated"], 1)
+                raise ConditionalSamplingError(
+                    f"{passes} passes of {m} rows delivered {sum(filled)} of {n} rows; the guard (min_dcr "
+                    f"{guard.min_dcr!r}) rejected {lg['rejected']} of {lg['generated']} generated rows "
+                    f"({100.0 * share:.1f} %)", filled, quotas, values)
+            burst = max(1, min(-(-open_rows // m), int(max_passes) - passes))
+            for _ in range(burst):
+                if use_graph:
+                    ent["graph"].replay()
+                else:
+                    self._guard_pass(ent, m)
+            passes += burst
+            filled = [int(x) for x in req["filled"].tolist()]     # the one readback per burst
+        out = ent["dst"][:n].clone()
+        report(passes, filled)
+        if hasattr(self.ops, "check"):
+            self.ops.check()
+        return out
+
+    def _guard_entry(self, m: int, nb: int, nf: int, n: int, guard, with_request: bool) -> dict:
+        """_cond_entry's buffers plus the guard's (packed pass, near, the search's scratch, its two counters), per
+        (m, bins, fixed columns, request or not) of one guard: a captured pass reads the guard's tables, so another
+        guard starts afresh."""
+        dev = self.device
+        if self._guard_ent and next(iter(self._guard_ent.values()))["guard"] is not guard:
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)
+            self._guard_ent = {}
+        key = (m, nb, nf, bool(with_request))
+        ent = self._guard_ent.get(key)
+        if ent is None:
+            H, lg, col, opt = self._gen_alloc(m, self.gen16)
+            i32 = lambda k: torch.zeros(k, dtype=torch.int32, device=dev)      # noqa: E731
+            i64 = lambda k: torch.zeros(k, dtype=torch.int64, device=dev)      # noqa: E731
+            f64 = lambda k: torch.zeros(k, dtype=torch.float64, device=dev)    # noqa: E731
+            ent = {"H": H, "lg": lg, "col": col, "opt": opt, "tgt": i32(m), "out": self._decoded(m),
+                   "req": {"drive": i32(2), "bin_opt": i32(nb), "bin_code": f64(nb), "quota": i64(nb),
+                           "filled": i64(nb), "seg_off": i64(nb), "fixed_j": i32(nf), "fixed_code": f64(nf),
+                           "stats": i64(2)},
+                   "guard": guard, "gbufs": guard.buffers(m), "gstats": i64(2), "request": bool(with_request),
+                   "dst": None, "graph": None}
+            self._guard_ent[key] = ent
+        if ent["dst"] is None or ent["dst"].shape[0] < n:
+            if ent["graph"] is not None:
+                torch.cuda.synchronize(dev)
+            ent["graph"] = None
+            ent["dst"] = self._decoded(n)
+        return ent
+
+    def _guard_pass(self, ent: dict, m: int):
+        o, req, guard = self.ops, ent["req"], ent["guard"]
+        H, lg, col, opt, tgt = ent["H"], ent["lg"], ent["col"], ent["opt"], ent["tgt"]
+        w16 = self._gen_weights16() if self.gen16 else None
+        o.sample_gen(self.gen_cond, H, self.c_cols, self.z_cols, col_out=col, opt_out=opt, stream_id=21)
+        if ent["request"]:
+            o.cond_request(req, col, opt, tgt, self.gen_cond, h=None if w16 is not None else H, c_col0=self.c_cols[0],
+                           stream_id=24)
+        else:
+            tgt.zero_()         # every row aims at the one bin
+        self._gen_forward(H, lg, col, opt, w16)
+        o.sample_decode(lg, ent["out"], self.gen_tables, stream_id=23)
+        guard.launch(ent["out"], *ent["gbufs"])
+        o.guard_mark(ent["gbufs"][2], tgt, ent["gstats"])
+        o.cond_partition(req, ent["out"], tgt, ent["dst"], any_value=not ent["request"])
+
+    def _capture_guard(self, ent: dict, m: int):
+        """Capture one guarded pass; the RNG counter, the request's and the guard's counters are put back after the
+        warm-up (see _capture_cond)."""
+        req, ctr = ent["req"], self.ops.ctr
+
+        def restore(ctr0):
+            ctr.copy_(ctr0)
+            req["filled"].zero_()
+            req["stats"].zero_()
+            ent["gstats"].zero_()
+        run = partial(self._guard_pass, ent, m)
         ent["graph"], = warm_and_capture(self.device, run, [run], snapshot=ctr.clone, restore=restore,
                                          mode=self.capture_mode)
 

@@ -60,15 +60,21 @@ class LoadedGenerator:
     vocabs: list
     _evaluators: dict = dataclasses.field(default_factory=dict, repr=False)   # kind -> (key, real frames, evaluator)
 
-    def sample(self, n: int, where=None, max_passes: int = 64) -> np.ndarray:
+    def sample(self, n: int, where=None, max_passes: int = 64, min_dcr=None, guard_real=None) -> np.ndarray:
         """[n, n_columns] decoded values (label codes for categoricals), float64.  A GPU table comes
         back through pinned host memory (torch's caching host allocator): 1M rows in ~9 ms instead
         of ~54 ms for a pageable copy.
 
         where ({column name: value | {value: weight}}, models/conditional.py): exactly n rows carrying the
         requested category values, grouped by the weighted column's values in request order; raises
-        ConditionalSamplingError when max_passes generation passes do not fill the request."""
-        return self._to_host(self.device_table(n, where=where, max_passes=max_passes))
+        ConditionalSamplingError when max_passes generation passes do not fill the request.
+
+        min_dcr (a float >= 0) with guard_real (the real table: a DataFrame or a CSV path): the privacy guard
+        (eval/privacy.py PrivacyGuard) -- no returned row lies within distance min_dcr of a real record, in the
+        privacy evaluator's metric; 0 keeps out exact copies.  Still exactly n rows, in generation order (with where:
+        the requested counts, grouped as above).  The real records have to be on this machine."""
+        return self._to_host(self.device_table(n, where=where, max_passes=max_passes, min_dcr=min_dcr,
+                                               guard_real=guard_real))
 
     @staticmethod
     def _to_host(vals: torch.Tensor) -> np.ndarray:
@@ -79,8 +85,12 @@ class LoadedGenerator:
         torch.cuda.current_stream(vals.device).synchronize()
         return host.numpy()
 
-    def write_csv(self, path: str, n: int, threads: int = 0, where=None, max_passes: int = 64) -> str:
-        vals = self.sample(n, where=where, max_passes=max_passes) if where else self.sample(n)
+    def write_csv(self, path: str, n: int, threads: int = 0, where=None, max_passes: int = 64, min_dcr=None,
+                  guard_real=None) -> str:
+        if min_dcr is not None:
+            vals = self.sample(n, where=where or None, max_passes=max_passes, min_dcr=min_dcr, guard_real=guard_real)
+        else:
+            vals = self.sample(n, where=where, max_passes=max_passes) if where else self.sample(n)
         return self._write_values(path, vals, threads)
 
     def _write_values(self, path: str, vals: np.ndarray, threads: int = 0) -> str:
@@ -115,19 +125,23 @@ class LoadedGenerator:
     def write_csv_all(self, path: str, n: int, score_real=None, privacy_real=None, corr_real=None, threads: int = 0,
                       where=None, max_passes: int = 64, utility_real=None, utility_test=None, utility_iters: int = 200,
                       utility_models=("lr",), utility_trees: int = 100, utility_depth: int = 12,
-                      utility_hidden: int = 100, utility_steps: int = 1000, utility_batch: int = 512):
+                      utility_hidden: int = 100, utility_steps: int = 1000, utility_batch: int = 512, min_dcr=None,
+                      guard_real=None):
         """:meth:`write_csv` with whichever of :meth:`score` (score_real), :meth:`privacy` (privacy_real),
         :meth:`correlation` (corr_real) and :meth:`utility` (utility_real, utility_test) are asked for, all of the
         rows the CSV holds and all taken on the device before the copy.  utility_models: ``"lr"`` (:meth:`utility`)
         and / or ``"dt"`` / ``"rf"`` (:meth:`tree_utility`, with utility_trees and utility_depth) and / or ``"mlp"``
         (:meth:`mlp_utility`, with utility_hidden, utility_steps and utility_batch), whose keys share the utility dict
-        in that order.  Returns ((Avg_JSD, Avg_WD) | None, privacy dict | None, correlation dict | None, utility
+        in that order.  min_dcr: the privacy guard of :meth:`sample`, against guard_real or, by default, privacy_real
+        (whose ``copies`` is then 0).  Returns ((Avg_JSD, Avg_WD) | None, privacy dict | None, correlation dict | None, utility
         dict | None)."""
         utility_models = tuple(utility_models)
         if not utility_models or set(utility_models) - {"lr", "dt", "rf", "mlp"}:
             raise ValueError("utility_models must be a non-empty subset of ('lr', 'dt', 'rf', 'mlp'), got "
                              f"{utility_models}")
-        vals = self.device_table(n, where=where, max_passes=max_passes)
+        if min_dcr is not None and guard_real is None:
+            guard_real = privacy_real
+        vals = self.device_table(n, where=where, max_passes=max_passes, min_dcr=min_dcr, guard_real=guard_real)
         sim = self._evaluator(score_real, n).score(vals) if score_real is not None else None
         priv = self._privacy_evaluator(privacy_real, n).score(vals) if privacy_real is not None else None
         corr = self._correlation_evaluator(corr_real, n).score(vals) if corr_real is not None else None
@@ -253,8 +267,32 @@ class LoadedGenerator:
         held = np.arange(len(train)) % 5 == 4
         return train[~held].reset_index(drop=True), train[held].reset_index(drop=True)
 
-    def device_table(self, n: int, where=None, max_passes: int = 64) -> torch.Tensor:
+    def _guard(self, real, min_dcr):
+        """The PrivacyGuard of radius min_dcr around ``real`` (kept per real table; a new radius shares its packed
+        table)."""
+        from ..eval.privacy import PrivacyGuard, squared_radius
+        squared_radius(min_dcr)
+        if real is None:
+            raise ValueError("min_dcr needs the real table to guard against (guard_real)")
+        dev = self.engine.device
+        base = self._cached("guard", (real,), (), lambda frame: PrivacyGuard(
+            frame, self.meta, self.vocabs, dev, min_dcr=min_dcr, ops=self.engine.ops))
+        if base.min_dcr != float(min_dcr):
+            base.min_dcr = float(min_dcr)
+            base.t2.fill_(squared_radius(min_dcr))       # (a captured pass reads t2 from the device)
+        return base
+
+    def device_table(self, n: int, where=None, max_passes: int = 64, min_dcr=None, guard_real=None) -> torch.Tensor:
         """:meth:`sample`'s table where the engine left it: [n, n_columns] float64 on the engine's device"""
+        if min_dcr is not None:
+            guard = self._guard(guard_real, min_dcr)
+            req = None
+            if where:
+                from .conditional import build_request
+                req = build_request(self.transformer, self.meta, self.vocabs, where, int(n), self.engine.device)
+            return self.engine.generate_decoded_guarded(int(n), guard, request=req, max_passes=max_passes)
+        if guard_real is not None:
+            raise ValueError("guard_real without min_dcr: give the radius (0 keeps out exact copies)")
         if where:
             from .conditional import build_request
             req = build_request(self.transformer, self.meta, self.vocabs, where, int(n), self.engine.device)

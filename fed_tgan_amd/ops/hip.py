@@ -584,7 +584,7 @@ class HipOps:
         self.L.cond_request(*self._cond_req(req), col, opt, tgt, h, int(c_col0), cond["cond_offset"],
                             cond["cond_width"], self.seed, self.ctr if ctr is None else ctr, int(stream_id) * 16)
 
-    def cond_partition(self, req, out, tgt, dst):
+    def cond_partition(self, req, out, tgt, dst, any_value=False):
         """Same contract (and bit-identical results) as TorchOps.cond_partition: flag + count, rank + copy, finish."""
         m, nb = int(out.shape[0]), int(req["quota"].numel())
         key = ("cond", m, nb)
@@ -596,7 +596,10 @@ class HipOps:
                   torch.empty(max(1, int(self.L.cond_partition_workgroups(m)) * nb), dtype=torch.int32,
                               device=self.device))
             self._dec[key] = sc
-        self.L.cond_partition(*self._cond_req(req), out, tgt, dst, sc[0], sc[1])
+        if any_value:
+            self.L.cond_partition(*self._cond_req(req), out, tgt, dst, sc[0], sc[1], True)
+        else:
+            self.L.cond_partition(*self._cond_req(req), out, tgt, dst, sc[0], sc[1])
 
     # ------------------------------------------------------------------ similarity evaluator
     SIM_SORT_TILE = 2048   # kernels/launch.h SIM_SORT_TILE: keys per sorted LDS tile / merged output tile
@@ -651,6 +654,15 @@ class HipOps:
     def nn_top2(self, q_cont, q_cat, r_cont, r_cat, exclude_self, d1, d2, i1, scratch):
         """Same contract as TorchOps.nn_top2; scratch: float64 [>= nn_scratch(nq, nr)]."""
         self.L.nn_top2(q_cont, q_cat, r_cont, r_cat, bool(exclude_self), d1, d2, i1, scratch)
+
+    def nn_within(self, q_cont, q_cat, r_cont, r_cat, t2, near, scratch):
+        """Same contract as TorchOps.nn_within (kernels/privacy.hip nn_within_kernel + its merge); scratch: float64
+        [>= nn_scratch(nq, nr)], as nn_top2's (half of it is used, as int32 per-chunk answers)."""
+        self.L.nn_within(q_cont, q_cat, r_cont, r_cat, t2, near, scratch)
+
+    def guard_mark(self, near, tgt, stats):
+        """Same contract as TorchOps.guard_mark."""
+        self.L.guard_mark(near, tgt, stats)
 
     def nn_stats(self, d1, d2, n, keys, tmp, part, out):
         """Same contract as TorchOps.nn_stats; tmp: scratch of keys' shape (the sort's), part: float64

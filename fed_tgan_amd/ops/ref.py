@@ -393,22 +393,24 @@ class TorchOps:
         opt[:m] = o.to(opt.dtype)
         tgt.copy_(t.to(tgt.dtype))
 
-    def cond_partition(self, req, out, tgt, dst):
+    def cond_partition(self, req, out, tgt, dst, any_value=False):
         """Move the rows of a decoded pass that carry every requested value into their bin's quota segment of dst.
 
         Row r is kept iff tgt[r] >= 0, out[r, drive[1]] == bin_code[tgt[r]] and out[r, fixed_j[k]] == fixed_code[k]
         for every k (exact float64 compares).  The kept rows of bin t, in row order, continue the bin's segment:
         the i-th of them goes to dst[seg_off[t] + filled[t] + i] while that index stays below seg_off[t] + quota[t];
         the rest are dropped.  Then filled[t] = min(quota[t], filled[t] + kept_t), stats[0] += rows and
-        stats[1] += kept rows (dropped ones included).  Nothing else of dst is written."""
+        stats[1] += kept rows (dropped ones included).  Nothing else of dst is written.  any_value: no value is
+        compared, a row is kept iff 0 <= tgt[r] < bins (the privacy guard without a request: one bin)."""
         m = out.shape[0]
         t = tgt[:m].long()
         nb = req["quota"].numel()
         keep = (t >= 0) & (t < nb)
         tc = t.clamp(0, nb - 1)
-        keep &= out[:, int(req["drive"][1])] == req["bin_code"][tc]
-        for j, code in zip(req["fixed_j"].tolist(), req["fixed_code"].tolist()):
-            keep &= out[:, int(j)] == code
+        if not any_value:
+            keep &= out[:, int(req["drive"][1])] == req["bin_code"][tc]
+            for j, code in zip(req["fixed_j"].tolist(), req["fixed_code"].tolist()):
+                keep &= out[:, int(j)] == code
         for b in range(nb):
             idx = torch.nonzero(keep & (t == b)).view(-1)
             q, f = int(req["quota"][b]), int(req["filled"][b])
@@ -579,6 +581,41 @@ class TorchOps:
             d1[q0:q1] = best
             d2[q0:q1] = dist.min(dim=1).values
             i1[q0:q1] = torch.where(none, torch.full_like(first, -1), first).to(i1.dtype)
+
+    def nn_within(self, q_cont, q_cat, r_cont, r_cat, t2, near, scratch=None):
+        """The privacy guard's radius test: near[i] (int32) = the lowest index of a reference row r with
+        d2(q_i, r) <= t2, or -1 where there is none.
+
+        d2 is nn_top2's: the continuous squared differences in column order plus the number of differing categorical
+        codes, in float64.  t2: a one-element float64 tensor on the queries' device (the squared radius; <= is
+        inclusive, so t2 = 0 flags exact copies and t2 = +inf every row whose distances are not NaN, with near = 0).
+        A distance that is NaN (a NaN query value, inf - inf) is within no radius.  Works on blocks of queries."""
+        nq, nr = q_cont.shape[0], r_cont.shape[0]
+        dev = q_cont.device
+        step = max(1, self.NN_PAIRS // max(nr, 1))
+        cols = torch.arange(nr, device=dev)
+        for q0 in range(0, nq, step):
+            q1 = min(nq, q0 + step)
+            dist = torch.zeros(q1 - q0, nr, dtype=torch.float64, device=dev)
+            for c in range(q_cont.shape[1]):
+                diff = q_cont[q0:q1, c, None] - r_cont[None, :, c]
+                dist += diff * diff
+            if q_cat.shape[1]:
+                miss = torch.zeros(q1 - q0, nr, dtype=torch.int32, device=dev)
+                for c in range(q_cat.shape[1]):
+                    miss += (q_cat[q0:q1, c, None] != r_cat[None, :, c]).to(torch.int32)
+                dist += miss.to(torch.float64)
+            first = torch.where(dist <= t2.reshape(()), cols[None, :], nr).min(dim=1).values
+            near[q0:q1] = torch.where(first < nr, first, torch.full_like(first, -1)).to(near.dtype)
+
+    def guard_mark(self, near, tgt, stats):
+        """tgt[i] = -1 (no row of a conditional pass with that target is kept) wherever near[i] >= 0, for the
+        tgt.numel() rows of a pass; stats (int64 [2]) += [rows tested, rows rejected]."""
+        m = tgt.shape[0]
+        rej = near[:m] >= 0
+        tgt[rej] = -1
+        stats[0] += m
+        stats[1] += int(rej.sum())
 
     def nn_stats(self, d1, d2, n, keys, tmp, part, out):
         """Table scores of rows [0, n): keys [2, >= n] receives DCR = sqrt(d1) and NNDR = sqrt(d1 / d2) (1 where
