@@ -1335,6 +1335,90 @@ int64_t nn_chunks(int64_t nr) { return fedtgan::nn_chunks(nr); }
 int64_t nn_scratch(int64_t nq, int64_t nr) { return fedtgan::nn_scratch_doubles(nq, nr); }
 int64_t nn_stats_part(int64_t n) { return 2 * (int64_t)fedtgan::nn_stats_blocks(n); }
 
+// ----------------------------------------------------------------------------- fidelity evaluator
+namespace {
+fedtgan::NnPairs nn_pairs(const char* what, const Tensor& q_cont, const Tensor& q_cat, const Tensor& r_cont,
+                          const Tensor& r_cat) {
+  TORCH_CHECK(sim_f64(q_cont) && q_cont.dim() == 2 && sim_i32(q_cat) && q_cat.dim() == 2 &&
+                  q_cat.size(0) == q_cont.size(0), what, ": queries float64 [nq, n_cont] and int32 [nq, n_cat]");
+  TORCH_CHECK(sim_f64(r_cont) && r_cont.dim() == 2 && sim_i32(r_cat) && r_cat.dim() == 2 &&
+                  r_cat.size(0) == r_cont.size(0) && r_cont.size(1) == q_cont.size(1) &&
+                  r_cat.size(1) == q_cat.size(1), what, ": reference rows with the queries' columns");
+  const int64_t nq = q_cont.size(0), nr = r_cont.size(0);
+  TORCH_CHECK(nr >= 1 && nr < (int64_t)INT32_MAX && nq < (int64_t)INT32_MAX && q_cont.size(1) + q_cat.size(1) >= 1,
+              what, ": at least one reference row and one column");
+  fedtgan::NnPairs p{};
+  p.nq = (int)nq;
+  p.nr = (int)nr;
+  p.n_cont = (int)q_cont.size(1);
+  p.n_cat = (int)q_cat.size(1);
+  p.q_cont = p.n_cont ? q_cont.data_ptr<double>() : nullptr;
+  p.r_cont = p.n_cont ? r_cont.data_ptr<double>() : nullptr;
+  p.q_cat = p.n_cat ? q_cat.data_ptr<int>() : nullptr;
+  p.r_cat = p.n_cat ? r_cat.data_ptr<int>() : nullptr;
+  return p;
+}
+}  // namespace
+
+void nn_topk(const Tensor& q_cont, const Tensor& q_cat, const Tensor& r_cont, const Tensor& r_cat, bool exclude_self,
+             int64_t k, const Tensor& out, const Tensor& scratch) {
+  fedtgan::NnTopkArgs a{};
+  a.p = nn_pairs("nn_topk", q_cont, q_cat, r_cont, r_cat);
+  TORCH_CHECK(k >= 1 && k <= fedtgan::FID_MAX_K, "nn_topk: k is 1..", fedtgan::FID_MAX_K, ", got ", k);
+  TORCH_CHECK(!exclude_self || a.p.nq == a.p.nr, "nn_topk: exclude_self compares a table with itself");
+  TORCH_CHECK(sim_f64(out) && out.numel() >= a.p.nq, "nn_topk: out float64, one entry per query");
+  const int64_t need = fedtgan::nn_topk_scratch_doubles(a.p.nq, a.p.nr, (int)k);
+  TORCH_CHECK(sim_f64(scratch) && scratch.numel() >= need, "nn_topk: scratch needs ", need, " float64");
+  if (a.p.nq == 0) return;
+  a.exclude_self = exclude_self ? 1 : 0;
+  a.k = (int)k;
+  a.out = out.data_ptr<double>();
+  fedtgan::launch_nn_topk(a, scratch.data_ptr<double>(), cur_stream());
+}
+
+void nn_ball(const Tensor& q_cont, const Tensor& q_cat, const Tensor& r_cont, const Tensor& r_cat, const Tensor& r_rad2,
+             const Tensor& cnt, const Tensor& dmin, const Tensor& scratch) {
+  fedtgan::NnBallArgs a{};
+  a.p = nn_pairs("nn_ball", q_cont, q_cat, r_cont, r_cat);
+  TORCH_CHECK(sim_f64(r_rad2) && r_rad2.numel() >= a.p.nr, "nn_ball: r_rad2 float64, one entry per reference row");
+  TORCH_CHECK(sim_i32(cnt) && cnt.numel() >= a.p.nq && sim_f64(dmin) && dmin.numel() >= a.p.nq,
+              "nn_ball: cnt int32 and dmin float64, one entry per query");
+  const int64_t need = fedtgan::nn_ball_scratch_doubles(a.p.nq, a.p.nr);
+  TORCH_CHECK(sim_f64(scratch) && scratch.numel() >= need, "nn_ball: scratch needs ", need, " float64");
+  if (a.p.nq == 0) return;
+  a.r_rad2 = r_rad2.data_ptr<double>();
+  a.cnt = cnt.data_ptr<int>();
+  a.dmin = dmin.data_ptr<double>();
+  fedtgan::launch_nn_ball(a, scratch.data_ptr<double>(), cur_stream());
+}
+
+void prdc_reduce(const Tensor& cnt_a, const Tensor& cnt_b, const Tensor& dmin_b, const Tensor& rr, int64_t n, int64_t m,
+                 int64_t k, const Tensor& scores) {
+  TORCH_CHECK(n >= 1 && m >= 1 && n < (int64_t)INT32_MAX && m < (int64_t)INT32_MAX && k >= 1 &&
+                  k <= fedtgan::FID_MAX_K, "prdc_reduce: n >= 1, m >= 1, k in 1..", fedtgan::FID_MAX_K);
+  TORCH_CHECK(sim_i32(cnt_a) && cnt_a.numel() >= n, "prdc_reduce: cnt_a int32 [>= n]");
+  TORCH_CHECK(sim_i32(cnt_b) && cnt_b.numel() >= m && sim_f64(dmin_b) && dmin_b.numel() >= m && sim_f64(rr) &&
+                  rr.numel() >= m, "prdc_reduce: cnt_b int32, dmin_b / rr float64, [>= m] each");
+  TORCH_CHECK(sim_f64(scores) && scores.numel() >= 4, "prdc_reduce: scores float64 [>= 4]");
+  fedtgan::PrdcArgs a{};
+  a.cnt_a = cnt_a.data_ptr<int>();
+  a.cnt_b = cnt_b.data_ptr<int>();
+  a.dmin_b = dmin_b.data_ptr<double>();
+  a.rr = rr.data_ptr<double>();
+  a.n = (int)n;
+  a.m = (int)m;
+  a.k = (int)k;
+  a.scores = scores.data_ptr<double>();
+  fedtgan::launch_prdc_reduce(a, cur_stream());
+}
+
+int64_t fid_max_k() { return fedtgan::FID_MAX_K; }
+int64_t nn_topk_scratch(int64_t nq, int64_t nr, int64_t k) {
+  TORCH_CHECK(k >= 1 && k <= fedtgan::FID_MAX_K, "nn_topk_scratch: k is 1..", fedtgan::FID_MAX_K);
+  return fedtgan::nn_topk_scratch_doubles(nq, nr, (int)k);
+}
+int64_t nn_ball_scratch(int64_t nq, int64_t nr) { return fedtgan::nn_ball_scratch_doubles(nq, nr); }
+
 // ----------------------------------------------------------------------------- correlation evaluator
 namespace {
 bool corr_i64(const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(); }
@@ -2312,6 +2396,18 @@ TORCH_LIBRARY(fedtgan, m) {
   m.def("nn_scratch(int nq, int nr) -> int", &nn_scratch);
   m.def("nn_stats_part(int n) -> int", &nn_stats_part);
   m.def(
+      "nn_topk(Tensor q_cont, Tensor q_cat, Tensor r_cont, Tensor r_cat, bool exclude_self, int k, Tensor(a!) out, "
+      "Tensor(b!) scratch) -> ()");
+  m.def(
+      "nn_ball(Tensor q_cont, Tensor q_cat, Tensor r_cont, Tensor r_cat, Tensor r_rad2, Tensor(a!) cnt, "
+      "Tensor(b!) dmin, Tensor(c!) scratch) -> ()");
+  m.def(
+      "prdc_reduce(Tensor cnt_a, Tensor cnt_b, Tensor dmin_b, Tensor rr, int n, int m, int k, Tensor(a!) scores) "
+      "-> ()");
+  m.def("fid_max_k() -> int", &fid_max_k);
+  m.def("nn_topk_scratch(int nq, int nr, int k) -> int", &nn_topk_scratch);
+  m.def("nn_ball_scratch(int nq, int nr) -> int", &nn_ball_scratch);
+  m.def(
       "corr_pack(Tensor values, Tensor kind, Tensor slot, Tensor card, Tensor(a!) cont, Tensor(b!) cat_t, "
       "Tensor(c!) mean, Tensor(d!) part) -> ()");
   m.def(
@@ -2431,6 +2527,9 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("guard_mark", &guard_mark);
   m.impl("nn_stats", &nn_stats);
   m.impl("nn_percentiles", &nn_percentiles);
+  m.impl("nn_topk", &nn_topk);
+  m.impl("nn_ball", &nn_ball);
+  m.impl("prdc_reduce", &prdc_reduce);
   m.impl("corr_pack", &corr_pack);
   m.impl("corr_moments", &corr_moments);
   m.impl("corr_counts", &corr_counts);

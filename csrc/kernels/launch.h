@@ -560,6 +560,48 @@ void launch_nn_stats(const double* d1, const double* d2, int n, double* keys, in
 // out[0..3] = 5th percentile of each (ascending) key row, smallest sqrt(d1), share of rows with d1 == 0
 void launch_nn_percentiles(const double* keys, int64_t ld, int n, const double* part, double* out, hipStream_t stream);
 
+// Fidelity evaluator (kernels/fidelity.hip): precision / recall / density / coverage of a decoded table against a real
+// one (Naeem et al. 2020), in the privacy evaluator's row space and metric, on its grid (NN_QUERY_TILE, NN_REF_TILE,
+// NN_CHUNK_ROWS).  Every distance of these kernels comes from one device function, so a distance of one pass and a
+// radius of another compare exactly.
+constexpr int FID_MAX_K = 8;          // the largest k: a (query, chunk) pair keeps its k smallest d2 in registers
+struct NnPairs {
+  const double* q_cont;   // [nq, n_cont]
+  const int* q_cat;       // [nq, n_cat]
+  const double* r_cont;   // [nr, n_cont]
+  const int* r_cat;       // [nr, n_cat]
+  int nq, nr, n_cont, n_cat;
+  int chunks;             // set by the launcher
+};
+struct NnTopkArgs {
+  NnPairs p;
+  int exclude_self;       // reference row j == query row i is no candidate
+  int k;                  // 1..FID_MAX_K
+  double* part;           // [chunks, k, nq] scratch: the k smallest d2 of a (query, chunk), ascending
+  double* out;            // [nq] the k-th smallest d2 over the candidates, with multiplicity (+inf: fewer than k)
+};
+int64_t nn_topk_scratch_doubles(int64_t nq, int64_t nr, int k);
+void launch_nn_topk(NnTopkArgs a, double* scratch, hipStream_t stream);
+struct NnBallArgs {
+  NnPairs p;
+  const double* r_rad2;   // [nr] squared radius of a reference row's ball (+inf: everything but NaN is inside)
+  int* part_cnt;          // [chunks, nq] scratch, carved by the launcher
+  double* part_min;       // [chunks, nq]
+  int* cnt;               // [nq] number of reference rows r with d2(q, r) <= r_rad2[r]
+  double* dmin;           // [nq] smallest d2(q, r) (+inf: every distance is NaN)
+};
+int64_t nn_ball_scratch_doubles(int64_t nq, int64_t nr);
+void launch_nn_ball(NnBallArgs a, double* scratch, hipStream_t stream);
+struct PrdcArgs {
+  const int* cnt_a;       // [n] real balls a generated row is inside
+  const int* cnt_b;       // [m] generated balls a real row is inside
+  const double* dmin_b;   // [m] a real row's distance to its nearest generated row
+  const double* rr;       // [m] a real row's squared radius
+  int n, m, k;
+  double* scores;         // [>= 4] precision, recall, density, coverage
+};
+void launch_prdc_reduce(const PrdcArgs& a, hipStream_t stream);
+
 // Correlation evaluator (kernels/correlation.hip): the [C, C] association matrix of a decoded table (Pearson r,
 // Theil's U, correlation ratio) and its distance to the real table's.  Every fp64 sum has a fixed order, counting
 // is in integers; no floating-point atomics, no allocation, no host round trip.

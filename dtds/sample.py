@@ -42,6 +42,11 @@ def main(argv=None):
                    help="also print one JSON line with Diff. Corr. of the generated rows against this table (the "
                         "distance between the two tables' association matrices, its mean and maximum per column "
                         "pair, and the real table's own even / odd row baseline)")
+    p.add_argument("-fidelity_against", default=None, metavar="REAL.csv",
+                   help="also print one JSON line, after all other output, with precision / recall / density / "
+                        "coverage of the generated rows against this table (k-nearest-neighbour manifold metrics) and "
+                        "the real table's own even / odd row baseline")
+    p.add_argument("-fidelity_k", type=int, default=5, help="the k of -fidelity_against (1..8)")
     p.add_argument("-utility_against", default=None, metavar="REAL.csv",
                    help="also print one JSON line with the ML utility of the generated rows: weighted F1 and accuracy "
                         "on held-out real rows of a logistic regression fitted on them on the device, the same for "
@@ -69,6 +74,10 @@ def main(argv=None):
     if (args.utility_hidden != 100 or args.utility_steps != 1000 or args.utility_batch != 512) and \
             not args.utility_against:
         p.error("-utility_hidden / -utility_steps / -utility_batch need -utility_against")
+    if args.fidelity_k != 5 and not args.fidelity_against:
+        p.error("-fidelity_k needs -fidelity_against")
+    if not 1 <= args.fidelity_k <= 8:
+        p.error("-fidelity_k is 1..8")
     guard_real = args.guard_against or args.privacy_against
     if args.min_dcr is not None and guard_real is None:
         p.error("-min_dcr needs a real table: -guard_against or -privacy_against")
@@ -84,15 +93,18 @@ def main(argv=None):
     gen = load_generator(args.model, dev, backend=args.backend, seed=args.seed)
     out = args.out or f"{gen.name}_synthetic.csv"
     t0 = time.time()
-    scores = privacy = corr = utility = None
-    if args.score_against or args.privacy_against or args.corr_against or args.utility_against:
-        scores, privacy, corr, utility = gen.write_csv_all(
+    scores = privacy = corr = utility = fidelity = None
+    if args.score_against or args.privacy_against or args.corr_against or args.utility_against or \
+            args.fidelity_against:
+        scores, privacy, corr, utility, *more = gen.write_csv_all(
             out, args.n, score_real=args.score_against, privacy_real=args.privacy_against,
             corr_real=args.corr_against, where=where or None, max_passes=args.max_passes,
             utility_real=args.utility_against, utility_test=args.utility_test, utility_iters=args.utility_iters,
             utility_models=utility_models, utility_trees=args.utility_trees, utility_depth=args.utility_depth,
             utility_hidden=args.utility_hidden, utility_steps=args.utility_steps, utility_batch=args.utility_batch,
-            min_dcr=args.min_dcr, guard_real=guard_real if args.min_dcr is not None else None)
+            min_dcr=args.min_dcr, guard_real=guard_real if args.min_dcr is not None else None,
+            fidelity_real=args.fidelity_against, fidelity_k=args.fidelity_k)
+        fidelity = more[0] if more else None
     elif args.min_dcr is not None:
         gen.write_csv(out, args.n, where=where or None, max_passes=args.max_passes, min_dcr=args.min_dcr,
                       guard_real=guard_real)
@@ -115,6 +127,8 @@ def main(argv=None):
         print(json.dumps(corr), flush=True)
     if utility is not None:
         print(json.dumps(utility), flush=True)
+    if fidelity is not None:
+        print(json.dumps(dict(fidelity, k=args.fidelity_k)), flush=True)
     return out
 
 

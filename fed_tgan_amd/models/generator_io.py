@@ -126,7 +126,7 @@ class LoadedGenerator:
                       where=None, max_passes: int = 64, utility_real=None, utility_test=None, utility_iters: int = 200,
                       utility_models=("lr",), utility_trees: int = 100, utility_depth: int = 12,
                       utility_hidden: int = 100, utility_steps: int = 1000, utility_batch: int = 512, min_dcr=None,
-                      guard_real=None):
+                      guard_real=None, fidelity_real=None, fidelity_k: int = 5):
         """:meth:`write_csv` with whichever of :meth:`score` (score_real), :meth:`privacy` (privacy_real),
         :meth:`correlation` (corr_real) and :meth:`utility` (utility_real, utility_test) are asked for, all of the
         rows the CSV holds and all taken on the device before the copy.  utility_models: ``"lr"`` (:meth:`utility`)
@@ -134,7 +134,8 @@ class LoadedGenerator:
         (:meth:`mlp_utility`, with utility_hidden, utility_steps and utility_batch), whose keys share the utility dict
         in that order.  min_dcr: the privacy guard of :meth:`sample`, against guard_real or, by default, privacy_real
         (whose ``copies`` is then 0).  Returns ((Avg_JSD, Avg_WD) | None, privacy dict | None, correlation dict | None, utility
-        dict | None)."""
+        dict | None).  With fidelity_real (and fidelity_k) the dict of :meth:`fidelity` for the same rows is appended
+        as a fifth element; without it the return value is the 4-tuple."""
         utility_models = tuple(utility_models)
         if not utility_models or set(utility_models) - {"lr", "dt", "rf", "mlp"}:
             raise ValueError("utility_models must be a non-empty subset of ('lr', 'dt', 'rf', 'mlp'), got "
@@ -145,6 +146,7 @@ class LoadedGenerator:
         sim = self._evaluator(score_real, n).score(vals) if score_real is not None else None
         priv = self._privacy_evaluator(privacy_real, n).score(vals) if privacy_real is not None else None
         corr = self._correlation_evaluator(corr_real, n).score(vals) if corr_real is not None else None
+        fid = self._fidelity_evaluator(fidelity_real, n, fidelity_k).score(vals) if fidelity_real is not None else None
         util = forest = mlp = None
         if utility_real is not None and "lr" in utility_models:
             util = self._utility_evaluator(utility_real, utility_test, n, utility_iters).score(vals)
@@ -160,6 +162,8 @@ class LoadedGenerator:
         for more in (forest, mlp):
             if more is not None:
                 out[3] = dict(out[3] or {}, **more.floats())
+        if fid is not None:
+            out.append(fid.floats())
         return tuple(out)
 
     def utility(self, train_real, test_real=None, n: int = 40000, where=None, max_passes: int = 64,
@@ -226,6 +230,21 @@ class LoadedGenerator:
     def _correlation_evaluator(self, real, n: int):
         from ..eval.correlation import DeviceCorrelation
         return self._table_evaluator("correlation", DeviceCorrelation, real, n)
+
+    def fidelity(self, real, n: int = 40000, where=None, max_passes: int = 64, k: int = 5) -> dict:
+        """Precision / recall / density / coverage of n generated rows against ``real`` (a DataFrame or a CSV path):
+        generated and scored on the engine's device (eval/fidelity.py), only the eight numbers come back:
+        ``precision`` / ``density`` (are the generated rows inside the real rows' k-nearest-neighbour balls),
+        ``recall`` / ``coverage`` (is every real row reached), and the real table's own even / odd row
+        ``precision_rr`` / ``recall_rr`` / ``density_rr`` / ``coverage_rr`` as the baseline, at half the table's
+        size.  The evaluator is kept per real table, n and k."""
+        return self._fidelity_evaluator(real, n, k).score(
+            self.device_table(n, where=where, max_passes=max_passes)).floats()
+
+    def _fidelity_evaluator(self, real, n: int, k: int = 5):
+        from ..eval.fidelity import DeviceFidelity
+        return self._cached("fidelity", (real,), (int(n), int(k)), lambda frame: DeviceFidelity(
+            frame, self.meta, self.vocabs, self.engine.device, ops=self.engine.ops, k=int(k), max_rows=int(n)))
 
     def privacy(self, real, n: int = 40000, where=None, max_passes: int = 64) -> dict:
         """DCR / NNDR of n generated rows against ``real`` (a DataFrame or a CSV path): generated and scored on the

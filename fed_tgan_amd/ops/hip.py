@@ -671,6 +671,31 @@ class HipOps:
         self.L.sim_sort(keys, tmp, int(n))
         self.L.nn_percentiles(keys, int(n), part, out)
 
+    # ------------------------------------------------------------------ fidelity evaluator (kernels/fidelity.hip)
+    FID_MAX_K = 8           # kernels/launch.h: the largest k (a register list per query and chunk)
+
+    @staticmethod
+    def nn_topk_scratch(nq: int, nr: int, k: int) -> int:
+        """float64 scratch elements nn_topk needs: k per (query, reference chunk)"""
+        return int(native.require().nn_topk_scratch(int(nq), int(nr), int(k)))
+
+    @staticmethod
+    def nn_ball_scratch(nq: int, nr: int) -> int:
+        """float64 scratch elements nn_ball needs: a minimum and an int32 count per (query, reference chunk)"""
+        return int(native.require().nn_ball_scratch(int(nq), int(nr)))
+
+    def nn_topk(self, q_cont, q_cat, r_cont, r_cat, exclude_self, k, out, scratch):
+        """Same contract as TorchOps.nn_topk; scratch: float64 [>= nn_topk_scratch(nq, nr, k)]."""
+        self.L.nn_topk(q_cont, q_cat, r_cont, r_cat, bool(exclude_self), int(k), out, scratch)
+
+    def nn_ball(self, q_cont, q_cat, r_cont, r_cat, r_rad2, cnt, dmin, scratch):
+        """Same contract as TorchOps.nn_ball; scratch: float64 [>= nn_ball_scratch(nq, nr)]."""
+        self.L.nn_ball(q_cont, q_cat, r_cont, r_cat, r_rad2, cnt, dmin, scratch)
+
+    def prdc_reduce(self, cnt_a, cnt_b, dmin_b, rr, n, m, k, scores):
+        """Same contract as TorchOps.prdc_reduce."""
+        self.L.prdc_reduce(cnt_a, cnt_b, dmin_b, rr, int(n), int(m), int(k), scores)
+
     # ------------------------------------------------------------------ correlation evaluator (kernels/correlation.hip)
     CORR_CONT, CORR_CAT = 0, 1
     CORR_CHUNK = 1024        # kernels/launch.h: rows per chunk of corr_moments (a row group is a whole number of them)

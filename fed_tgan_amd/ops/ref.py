@@ -640,6 +640,80 @@ class TorchOps:
         out[2] = keys[0, 0]
         out[3] = (a == 0).sum().to(torch.float64) / n
 
+    # ------------------------------------------------------------------ fidelity evaluator
+    FID_MAX_K = 8                                                # kernels/launch.h: the largest k
+
+    @staticmethod
+    def nn_topk_scratch(nq: int, nr: int, k: int) -> int:
+        return 1
+
+    @staticmethod
+    def nn_ball_scratch(nq: int, nr: int) -> int:
+        return 1
+
+    def _nn_blocks(self, q_cont, q_cat, r_cont, r_cat):
+        """(q0, q1, the [q1 - q0, nr] float64 block of d2) over blocks of queries, nn_top2's d2 and block size"""
+        nq, nr = q_cont.shape[0], r_cont.shape[0]
+        dev = q_cont.device
+        step = max(1, self.NN_PAIRS // max(nr, 1))
+        for q0 in range(0, nq, step):
+            q1 = min(nq, q0 + step)
+            dist = torch.zeros(q1 - q0, nr, dtype=torch.float64, device=dev)
+            for c in range(q_cont.shape[1]):
+                diff = q_cont[q0:q1, c, None] - r_cont[None, :, c]
+                dist += diff * diff
+            if q_cat.shape[1]:
+                miss = torch.zeros(q1 - q0, nr, dtype=torch.int32, device=dev)
+                for c in range(q_cat.shape[1]):
+                    miss += (q_cat[q0:q1, c, None] != r_cat[None, :, c]).to(torch.int32)
+                dist += miss.to(torch.float64)
+            yield q0, q1, dist
+
+    def nn_topk(self, q_cont, q_cat, r_cont, r_cat, exclude_self, k, out, scratch=None):
+        """out[i] = the k-th smallest squared distance (nn_top2's d2) of query row i to the reference rows, counted
+        with multiplicity; +inf where there are fewer than k candidates.  1 <= k <= FID_MAX_K.  exclude_self:
+        reference row i is no candidate of query i.  A NaN distance is no candidate.  Works on blocks of queries."""
+        k = int(k)
+        if not 1 <= k <= self.FID_MAX_K:
+            raise ValueError(f"nn_topk: k is 1..{self.FID_MAX_K}, got {k}")
+        nr = r_cont.shape[0]
+        inf = float("inf")
+        for q0, q1, dist in self._nn_blocks(q_cont, q_cat, r_cont, r_cat):
+            if exclude_self:
+                rows = torch.arange(q1 - q0, device=dist.device)
+                own = rows + q0
+                ok = own < nr
+                dist[rows[ok], own[ok]] = inf
+            dist = torch.where(torch.isnan(dist), torch.full_like(dist, inf), dist)
+            if nr < k:
+                out[q0:q1] = inf
+            else:
+                out[q0:q1] = torch.topk(dist, k, dim=1, largest=False).values[:, k - 1]
+
+    def nn_ball(self, q_cont, q_cat, r_cont, r_cat, r_rad2, cnt, dmin, scratch=None):
+        """cnt[i] (int32) = the number of reference rows r with d2(q_i, r) <= r_rad2[r] (inclusive; a radius of +inf
+        holds every distance that is no NaN), dmin[i] = the smallest d2(q_i, r) (+inf where every distance is NaN).
+        d2 is nn_top2's.  Works on blocks of queries."""
+        nr = r_cont.shape[0]
+        rad = r_rad2[:nr]
+        for q0, q1, dist in self._nn_blocks(q_cont, q_cat, r_cont, r_cat):
+            cnt[q0:q1] = (dist <= rad[None, :]).sum(dim=1).to(cnt.dtype)
+            dmin[q0:q1] = torch.where(torch.isnan(dist), torch.full_like(dist, float("inf")), dist).min(dim=1).values
+
+    def prdc_reduce(self, cnt_a, cnt_b, dmin_b, rr, n, m, k, scores):
+        """scores[0:4] = precision, recall, density, coverage (eval/fidelity.py) of n generated rows (cnt_a int32
+        [>= n]) against m real rows (cnt_b int32, dmin_b / rr float64, [>= m]): integer sums in int64, one float64
+        division each (by a tensor: torch may turn a division by a Python number into a product with its reciprocal,
+        which rounds twice)."""
+        n, m, k = int(n), int(m), int(k)
+        a, b = cnt_a[:n].to(torch.int64), cnt_b[:m]
+        f64 = torch.float64
+        den = lambda v: torch.full((), float(v), dtype=f64, device=scores.device)      # noqa: E731
+        scores[0] = (a > 0).sum().to(f64) / den(n)
+        scores[1] = (b > 0).sum().to(f64) / den(m)
+        scores[2] = a.sum().to(f64) / den(k * n)
+        scores[3] = (dmin_b[:m] <= rr[:m]).sum().to(f64) / den(m)
+
     # ------------------------------------------------------------------ correlation evaluator
     CORR_CONT, CORR_CAT = 0, 1
     CORR_CHUNK, CORR_LDS_BINS = 1024, 16384     # the HIP kernels' row chunk and LDS table limit; shared attributes only
