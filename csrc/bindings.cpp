@@ -2180,6 +2180,12 @@ int64_t set_tuning(const std::string& key, int64_t value) {
     fedtgan::g_bn_threads = (int)value;
     return prev;
   }
+  if (key == "bn_slices") {   // paired training BN: 1 one workgroup per column block, 2 / 4 row-storing workgroups per batch
+    TORCH_CHECK(value == 1 || value == 2 || value == 4, "bn_slices: 1, 2 or 4");
+    const int prev = fedtgan::g_bn_slices;
+    fedtgan::g_bn_slices = (int)value;
+    return prev;
+  }
   if (key == "act_rowreg_narrow") {   // rows <= 512 wide: per-wave kernels (0), row kernels 2-4 waves (1), a block per wave (2)
     TORCH_CHECK(value >= 0 && value <= 2, "act_rowreg_narrow: 0, 1 or 2");
     const int prev = fedtgan::g_act_rowreg_narrow;

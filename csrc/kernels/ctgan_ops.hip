@@ -916,7 +916,23 @@ __global__ __launch_bounds__(NW * 64) void activate_rowblk_kernel(const float* _
   float xv = x[jc];
   const int ic = einfo[jc];
   const float ar = a[jc];
+  // the slerp's condition columns (j >= D) of the real and fake rows: the sampler wrote them, nothing below does,
+  // so they are requested here with the logits and not behind the softmax's two barriers (a row without slerp
+  // re-requests its own element; masked below)
+  constexpr int TU = 2;
+  float ra[TU], fb[TU];
+#pragma unroll
+  for (int u = 0; u < TU; ++u) {
+    const int jt = do_sl ? min(D + u * NTH + tid, sl.cols - 1) : jc;
+    ra[u] = a[jt];
+    fb[u] = y[jt];
+  }
   const uint64_t step = ctr ? *ctr : 0ull;
+  float alpha = 0.f;     // the row's interpolation draw, off the path behind the barriers as well
+  if (do_sl) {
+    RngArgs srng{seed, ctr, sl.stream};
+    alpha = u01(rng4(srng, step, (uint64_t)r).x);
+  }
   if (in) {
     RngArgs rng{seed, ctr, stream_id};
     const uint4 u4 = rng4(rng, step, ((uint64_t)r << 20) + (uint64_t)(wv >> 2) * 64u + (uint64_t)lane);
@@ -962,16 +978,8 @@ __global__ __launch_bounds__(NW * 64) void activate_rowblk_kernel(const float* _
     sbb = xv * xv;
     sab = ar * xv;
   }
-  constexpr int TU = 2;
-  float ra[TU], fb[TU];
 #pragma unroll
-  for (int u = 0; u < TU; ++u) {     // the condition columns (j >= D) of the real and fake rows
-    const int jt = min(D + u * NTH + tid, sl.cols - 1);
-    ra[u] = a[jt];
-    fb[u] = y[jt];
-  }
-#pragma unroll
-  for (int u = 0; u < TU; ++u)
+  for (int u = 0; u < TU; ++u)     // the condition columns requested at the top
     if (D + u * NTH + tid < sl.cols) {
       saa += ra[u] * ra[u];
       sbb += fb[u] * fb[u];
@@ -984,8 +992,6 @@ __global__ __launch_bounds__(NW * 64) void activate_rowblk_kernel(const float* _
     sab += ra2 * fb2;
   }
   const float3 tot = block_sum3<NW>(saa, sbb, sab, red);
-  RngArgs srng{seed, ctr, sl.stream};
-  const float alpha = u01(rng4(srng, step, (uint64_t)r).x);
   float wa, wb;
   slerp_weights(tot.x, tot.y, tot.z, alpha, wa, wb);
   float* o = sl.out + (size_t)r * sl.ld;
@@ -1974,6 +1980,9 @@ void launch_colsum(const ColsumJob* jobs, int n_jobs, hipStream_t stream) {
 constexpr int BN_THREADS = 512, BN_WAVES = BN_THREADS / 64;
 int g_bn_cols = 8;    // columns per workgroup (tuning knob, see set_tuning)
 int g_bn_threads = 512;   // threads per BN workgroup: 512, or 1024 (half the rows per thread; set_tuning("bn_threads"))
+// workgroups per batch that store the paired launch's rows (set_tuning("bn_slices")): 1 is bn_relu_train_kernel,
+// 2 or 4 bn_relu_train_sliced_kernel.  2 measured fastest (profiles/bn_slices_r7.md: 5.73 / 4.63 / 5.47 us)
+int g_bn_slices = 2;
 // (16 columns for batched launches measured +1.0 ms per 8-client epoch once the clients sit on their own XCDs:
 // 47.7 vs 48.7 ms, profiles/batched_r4.md; 8 everywhere)
 static int bn_cols_for_launch() { return g_bn_cols; }
@@ -2127,6 +2136,93 @@ __global__ __launch_bounds__(NTH) void bn_relu_train_kernel(
     const int r = grp + i * GROUPS;
     if (r < rows) {
       const float n = bn_nhat(x[i], r >= rpg ? st1 : st0);
+      nhat[(size_t)r * ldn + c] = n;
+      out[(size_t)r * ldo + c] = bn_affine_relu(n, gm, bt);
+    }
+  }
+}
+
+// The paired launch (two batches) sliced over 1 + 2 S workgroups per column block, grid (column blocks, 1 + 2 S):
+// the 32 workgroups of bn_relu_train_kernel store 2 x 16 rows per thread behind the reduction, and that store
+// tail is what the launch waits for (profiles/bn_slices_r7.md, profiles/step_roundtrips_r14.md).
+//   blockIdx.y == 0      loads every row like bn_relu_train_kernel and writes only mean / invstd / rm / rv;
+//   blockIdx.y == 1 + b S + s   recomputes batch b's statistics from all of b's rows -- the same rows per thread in
+//                        the same order, the same butterfly and LDS combine, so the same bits -- and stores
+//                        nhat / out for slice s of the batch's row groups.
+// No workgroup waits on another, nothing is atomic and ``a`` is only read, so ``out`` / ``nhat`` must not alias it.
+// A thread's rows of one batch are NB = MAXR / 2 + 1 consecutive row groups starting at (b rpg) / GROUPS.
+template <int COLS, int MAXR>
+__global__ __launch_bounds__(BN_THREADS) void bn_relu_train_sliced_kernel(
+    const float* __restrict__ a, int lda, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float* __restrict__ out, int ldo, float* __restrict__ nhat, int ldn, float* __restrict__ mean,
+    float* __restrict__ invstd, float* __restrict__ rm, float* __restrict__ rv, int rows, int cols, int slices,
+    float momentum, float eps) {
+  constexpr int GROUPS = BN_THREADS / COLS, NB = MAXR / 2 + 1;
+  __shared__ float sh[2 * BN_MAXG * BN_WAVES * COLS];
+  const int lc = threadIdx.x % COLS, grp = threadIdx.x / COLS;
+  const int c = blockIdx.x * COLS + lc;
+  const bool ok = c < cols;
+  const int cc = min(c, cols - 1);
+  const int rpg = rows / 2;
+  if (blockIdx.y == 0) {   // the running statistics: bn_relu_train_kernel without its row stores
+    const float sh0 = a[cc], sh1 = a[(size_t)rpg * lda + cc];
+    const float rm0 = rm[cc], rv0 = rv[cc];
+    float x[MAXR];
+    float s[2 * BN_MAXG] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < MAXR; ++i) x[i] = a[(size_t)min(grp + i * GROUPS, rows - 1) * lda + cc];
+    bn_loads_issued();
+#pragma unroll
+    for (int i = 0; i < MAXR; ++i) {
+      const int r = grp + i * GROUPS;
+      const bool g1 = r >= rpg;
+      const float dv = x[i] - (g1 ? sh1 : sh0);
+      const float d = (r < rows) ? dv : 0.f;
+      if (g1) bn_acc(s[1], s[3], d); else bn_acc(s[0], s[2], d);
+    }
+    bn_colsum<COLS, 2 * BN_MAXG>(s, sh);
+    if (grp != 0 || !ok) return;
+    const BnStat st0 = bn_stat(s[0], s[2], sh0, rpg, eps), st1 = bn_stat(s[1], s[3], sh1, rpg, eps);
+    const float unb = bn_unbias(rpg);
+    float m = rm0, v = rv0;
+    mean[c] = st0.mu;
+    invstd[c] = st0.is;
+    bn_ema(m, v, st0, momentum, unb);          // batch after batch, in row order
+    mean[(size_t)cols + c] = st1.mu;
+    invstd[(size_t)cols + c] = st1.is;
+    bn_ema(m, v, st1, momentum, unb);
+    rm[c] = m;
+    rv[c] = v;
+    return;
+  }
+  const int role = (int)blockIdx.y - 1, b = role / slices, sl = role - b * slices;
+  const int lo = b * rpg, hi = lo + rpg;   // the batch's rows; the thread's are grp + (i0 + j) GROUPS
+  const int i0 = lo / GROUPS;
+  const float shift = a[(size_t)lo * lda + cc];
+  const float gm = gamma[cc], bt = beta[cc];
+  float x[NB];
+  float s[2] = {0.f, 0.f};   // sum d, sum d^2
+#pragma unroll
+  for (int j = 0; j < NB; ++j) x[j] = a[(size_t)min(grp + (i0 + j) * GROUPS, rows - 1) * lda + cc];
+  bn_loads_issued();
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const int r = grp + (i0 + j) * GROUPS;
+    // a row of the other batch adds +0 here, as it adds nothing to this batch's sums in the unsliced kernel
+    // (the sums start at +0 and never become -0, so x + 0 keeps every bit)
+    const float dv = x[j] - shift;
+    const float d = (r >= lo && r < hi) ? dv : 0.f;
+    bn_acc(s[0], s[1], d);
+  }
+  bn_colsum<COLS, 2>(s, sh);
+  const BnStat st = bn_stat(s[0], s[1], shift, rpg, eps);
+  if (!ok) return;
+  const int jlo = sl * NB / slices, jhi = (sl + 1) * NB / slices;
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const int r = grp + (i0 + j) * GROUPS;
+    if (j >= jlo && j < jhi && r >= lo && r < hi) {
+      const float n = bn_nhat(x[j], st);
       nhat[(size_t)r * ldn + c] = n;
       out[(size_t)r * ldo + c] = bn_affine_relu(n, gm, bt);
     }
@@ -2338,7 +2434,22 @@ static void bn_train_cols(const float* a, int lda, const float* gamma, const flo
                        cols, groups, momentum, eps, cb);
     return;
   }
-#define BN_TRAIN_LAUNCH(R)                                                                                          \
+  // two batches of one client on up to 16 rows per thread, written beside the input: the sliced grid
+  const auto apart = [&](const float* p, int ld) {
+    return p + (size_t)rows * ld <= a || a + (size_t)rows * lda <= p;
+  };
+  if (g_bn_slices > 1 && g_bn_threads == 512 && groups == 2 && cb.k == 1 && rows <= 16 * GROUPS && apart(out, ldo) && apart(nhat, ldn)) {
+    const dim3 sgrid(grid.x, 1 + 2 * g_bn_slices);
+#define BN_SLICED_LAUNCH(R)                                                                                         \
+  hipLaunchKernelGGL((bn_relu_train_sliced_kernel<COLS, R>), sgrid, block, 0, stream, a, lda, gamma, beta, out, ldo, \
+                     nhat, ldn, mean, invstd, rm, rv, rows, cols, g_bn_slices, momentum, eps)
+    if (rows <= 4 * GROUPS) BN_SLICED_LAUNCH(4);
+    else if (rows <= 8 * GROUPS) BN_SLICED_LAUNCH(8);
+    else BN_SLICED_LAUNCH(16);
+#undef BN_SLICED_LAUNCH
+    return;
+  }
+#define BN_TRAIN_LAUNCH(R)                                                                                        \
   hipLaunchKernelGGL((client_batch().xcd ? bn_relu_train_kernel<COLS, R, true> : bn_relu_train_kernel<COLS, R, false>), grid, block, 0, stream, a, lda, gamma, beta, out, ldo, nhat, \
                      ldn, mean, invstd, rm, rv, rows, cols, groups, momentum, eps, cb)
   if (rows <= 4 * GROUPS) BN_TRAIN_LAUNCH(4);

@@ -1176,6 +1176,31 @@ __global__ __launch_bounds__(256) void chain_epilogue_kernel(GemmArgs g, GemmArg
 #pragma unroll
     for (int k = 0; k < (PRE ? PQ : 1); ++k) wp[k] = w4[k];
   }
+  // ... and so are the operands of the tail's epilogue (the kq == 0 wave's: bias, the mask or the head seed's
+  // factors, the dropout counter): none depends on the head's row, so they travel with the weights instead of
+  // costing a round trip of their own behind the dot products' barrier.  Clamped addresses, used under the
+  // epilogue's own bounds.
+  float e_bias = 0.f, e_hv = 0.f, e_ms[ROWS], e_hc[ROWS];
+  uint64_t e_st = 0ull;
+  if constexpr (PRE) {
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) e_ms[r] = e_hc[r] = 0.f;
+    if ((threadIdx.x >> 6) == 0) {
+      const int jp = min(s * CH_COLS + (int)threadIdx.x, t.N - 1);
+      if (t.bias) e_bias = t.bias[jp];
+      if constexpr (MASK) {
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) e_ms[r] = t.ms[(size_t)min(m0 + r, g.M - 1) * t.ldms + jp];
+      } else {
+        if (t.epi == EPI_LRELU_DROPOUT && t.rng_ctr) e_st = *t.rng_ctr;
+        if (t.epi == EPI_LRELU_DROPOUT && t.head_a) {
+          e_hv = t.head_v[jp];
+#pragma unroll
+          for (int r = 0; r < ROWS; ++r) e_hc[r] = t.head_coef[min(m0 + r, g.M - 1)];
+        }
+      }
+    }
+  }
   for (int n = threadIdx.x; n < g.N; n += blockDim.x) {
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
@@ -1273,6 +1298,24 @@ __global__ __launch_bounds__(256) void chain_epilogue_kernel(GemmArgs g, GemmArg
       const int m = m0 + r;
       if (ROWS > 1 && m >= g.M) break;
       float v = t.alpha * ((part[r][0][jl] + part[r][1][jl]) + (part[r][2][jl] + part[r][3][jl]));
+      if constexpr (PRE) {   // the operands requested at the top (apply_epi's expressions, nothing reloaded)
+        if (t.bias) v += e_bias;
+        if constexpr (MASK) {
+          t.c[(size_t)m * t.ldc + j] = v * e_ms[r];
+        } else if (t.epi == EPI_LRELU_DROPOUT) {
+          const float sl = v > 0.f ? 1.f : t.slope;
+          RngArgs rng{t.seed, t.rng_ctr, t.rng_stream};
+          const uint4 rr = rng4(rng, e_st, (uint64_t)m * t.N + j);
+          const float keep = (u01(rr.x) >= t.p_drop) ? 1.f / (1.f - t.p_drop) : 0.f;
+          const float f = sl * keep;
+          t.ms[(size_t)m * t.ldms + j] = f;
+          if (t.head_a) t.head_a[(size_t)m * t.ldha + j] = e_hc[r] * e_hv * f;
+          t.c[(size_t)m * t.ldc + j] = v * f;
+        } else {
+          t.c[(size_t)m * t.ldc + j] = apply_epi(t, v, m, j, e_st, (uint64_t)m * t.N + j);
+        }
+        continue;
+      }
       if (t.bias) v += t.bias[j];
       if constexpr (MASK) t.c[(size_t)m * t.ldc + j] = v * t.ms[(size_t)m * t.ldms + j];
       else t.c[(size_t)m * t.ldc + j] = apply_epi(t, v, m, j, st, (uint64_t)m * t.N + j);

@@ -224,6 +224,7 @@ extern int g_chain_pre;         // set_tuning("chain_pre")
 extern int g_chain_rows;        // set_tuning("chain_rows")
 extern int g_gp_threads;   // register-resident gp_scale workgroup size (set_tuning("gp_threads"))
 extern int g_bn_threads;   // BN workgroup size (set_tuning("bn_threads"))
+extern int g_bn_slices;    // paired training BN: workgroups per batch that store rows (set_tuning("bn_slices"))
 extern int g_act_rowreg_narrow;   // narrow rows on the register-resident row kernels (set_tuning("act_rowreg_narrow"))
 
 // Weight gradient of a one-hot conditional input block (generator layers, input-major weights): row k of the
