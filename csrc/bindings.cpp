@@ -1115,6 +1115,88 @@ void cond_partition(const Tensor& drive, const Tensor& bin_opt, const Tensor& bi
 
 int64_t cond_partition_workgroups(int64_t rows) { return fedtgan::cond_partition_workgroups((int)rows); }
 
+// range / set predicates of a conditional request (kernels/cond_pred.hip)
+void pred_request(const Tensor& drv, const Tensor& drv_opt, const Tensor& drv_cum, const Tensor& quota,
+                  const Tensor& filled, const Tensor& col, const Tensor& opt, const Tensor& tgt,
+                  const optional<Tensor>& h, int64_t cc, const Tensor& cond_off, const Tensor& cond_w, int64_t seed,
+                  const Tensor& rng_ctr, int64_t stream) {
+  auto i32 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(); };
+  auto i64 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(); };
+  fedtgan::PredRequestArgs a{};
+  a.M = (int)drv_opt.numel();
+  TORCH_CHECK(i32(drv) && drv.numel() == 2 && i32(drv_opt) && a.M >= 1 && drv_cum.is_cuda() &&
+                  drv_cum.scalar_type() == at::kDouble && drv_cum.is_contiguous() && drv_cum.numel() == a.M,
+              "pred_request: drv int32 [2], drv_opt int32 [M], drv_cum float64 [M], M >= 1");
+  TORCH_CHECK(i64(quota) && quota.numel() == 1 && i64(filled) && filled.numel() == 1,
+              "pred_request: a predicate-driven request has one bin (int64 quota / filled)");
+  a.rows = (int)tgt.numel();
+  for (const Tensor* t : {&col, &opt, &tgt})
+    TORCH_CHECK(i32(*t) && t->numel() >= a.rows, "pred_request: col / opt / tgt must be int32 with one entry per row");
+  TORCH_CHECK(i32(cond_off) && i32(cond_w) && cond_w.numel() == cond_off.numel() && cond_off.numel() >= 1,
+              "pred_request: int32 span tables");
+  a.drv = drv.data_ptr<int>();
+  a.drv_opt = drv_opt.data_ptr<int>();
+  a.drv_cum = drv_cum.data_ptr<double>();
+  a.quota = quota.data_ptr<int64_t>();
+  a.filled = filled.data_ptr<int64_t>();
+  a.col = col.data_ptr<int>();
+  a.opt = opt.data_ptr<int>();
+  a.tgt = tgt.data_ptr<int>();
+  a.cond_off = cond_off.data_ptr<int>();
+  a.cond_w = cond_w.data_ptr<int>();
+  a.n_span = (int)cond_off.numel();
+  if (h.has_value() && h->defined()) {
+    check_f32_2d(*h, "pred_request h");
+    TORCH_CHECK(h->size(0) >= a.rows && cc >= 0 && cc < h->size(1), "pred_request: h rows / conditional block");
+    a.h = fp(*h);
+    a.ldh = ld_of(*h);
+    a.cc = (int)cc;
+    a.C = (int)(h->size(1) - cc);
+  }
+  a.seed = (uint64_t)seed;
+  a.rng_ctr = ctr_ptr(rng_ctr);
+  a.rng_stream = (uint32_t)stream;
+  fedtgan::launch_pred_request(a, cur_stream());
+}
+
+void pred_mark(const Tensor& pred_j, const Tensor& pred_kind, const Tensor& pred_lo, const Tensor& pred_hi,
+               const Tensor& pred_lut_off, const Tensor& pred_lut_len, const Tensor& pred_lut,
+               const Tensor& pred_stats, const Tensor& out, const Tensor& tgt) {
+  auto i32 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(); };
+  auto f64 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kDouble && t.is_contiguous(); };
+  const int64_t np = pred_j.numel();
+  TORCH_CHECK(np >= 0 && np <= fedtgan::PRED_MAX, "pred_mark: at most ", fedtgan::PRED_MAX, " predicates");
+  TORCH_CHECK(i32(pred_j) && i32(pred_kind) && pred_kind.numel() == np && i32(pred_lut_off) &&
+                  pred_lut_off.numel() == np && i32(pred_lut_len) && pred_lut_len.numel() == np,
+              "pred_mark: int32 column / kind / table slice per predicate");
+  TORCH_CHECK(f64(pred_lo) && pred_lo.numel() == np && f64(pred_hi) && pred_hi.numel() == np,
+              "pred_mark: float64 bounds per predicate");
+  TORCH_CHECK(pred_lut.is_cuda() && pred_lut.scalar_type() == at::kByte && pred_lut.is_contiguous() &&
+                  pred_lut.numel() < (int64_t)INT32_MAX, "pred_mark: pred_lut uint8");
+  TORCH_CHECK(pred_stats.is_cuda() && pred_stats.scalar_type() == at::kLong && pred_stats.is_contiguous() &&
+                  pred_stats.numel() == 2 + fedtgan::PRED_MAX, "pred_mark: pred_stats int64 [2 + PRED_MAX]");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kDouble && out.is_contiguous() && out.dim() == 2,
+              "pred_mark: out must be contiguous float64 [rows, n_cols]");
+  TORCH_CHECK(i32(tgt) && tgt.numel() >= out.size(0) && out.size(0) < (int64_t)INT32_MAX,
+              "pred_mark: tgt int32, one entry per row");
+  fedtgan::PredMarkArgs a{};
+  a.p.n_pred = (int)np;
+  a.p.j = pred_j.data_ptr<int>();
+  a.p.kind = pred_kind.data_ptr<int>();
+  a.p.lo = pred_lo.data_ptr<double>();
+  a.p.hi = pred_hi.data_ptr<double>();
+  a.p.lut_off = pred_lut_off.data_ptr<int>();
+  a.p.lut_len = pred_lut_len.data_ptr<int>();
+  a.p.lut = pred_lut.data_ptr<uint8_t>();
+  a.p.lut_total = (int)pred_lut.numel();
+  a.p.stats = pred_stats.data_ptr<int64_t>();
+  a.out = out.data_ptr<double>();
+  a.rows = (int)out.size(0);
+  a.n_cols = (int)out.size(1);
+  a.tgt = tgt.data_ptr<int>();
+  fedtgan::launch_pred_mark(a, cur_stream());
+}
+
 // ----------------------------------------------------------------------------- similarity evaluator
 namespace {
 bool sim_i32(const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(); }
@@ -2119,7 +2201,8 @@ void vgm_fit(const Tensor& x, const Tensor& n_rows, const c10::optional<Tensor>&
 int64_t check_status() {
   (void)hipDeviceSynchronize();
   return (int64_t)(fedtgan::check_status_gemm() | fedtgan::check_status_ctgan_ops() | fedtgan::check_status_vgm() |
-                   fedtgan::check_status_cond_gen() | fedtgan::check_status_similarity() |
+                   fedtgan::check_status_cond_gen() | fedtgan::check_status_cond_pred() |
+                   fedtgan::check_status_similarity() |
                    fedtgan::check_status_forest());
 }
 
@@ -2374,6 +2457,13 @@ TORCH_LIBRARY(fedtgan, m) {
       "Tensor(e!) counts, bool any_value=False) -> ()");
   m.def("cond_partition_workgroups(int rows) -> int", &cond_partition_workgroups);
   m.def(
+      "pred_request(Tensor drv, Tensor drv_opt, Tensor drv_cum, Tensor quota, Tensor filled, Tensor(a!) col, "
+      "Tensor(b!) opt, Tensor(c!) tgt, Tensor(d!)? h, int cc, Tensor cond_off, Tensor cond_w, int seed, "
+      "Tensor rng_ctr, int stream) -> ()");
+  m.def(
+      "pred_mark(Tensor pred_j, Tensor pred_kind, Tensor pred_lo, Tensor pred_hi, Tensor pred_lut_off, "
+      "Tensor pred_lut_len, Tensor pred_lut, Tensor(a!) pred_stats, Tensor out, Tensor(b!) tgt) -> ()");
+  m.def(
       "sim_prepare(Tensor values, Tensor kind, Tensor slot, Tensor vocab, Tensor(a!) keys, Tensor(b!) valid, "
       "Tensor(c!) counts) -> ()");
   m.def("sim_sort(Tensor(a!) keys, Tensor(b!) tmp, int n) -> ()");
@@ -2522,6 +2612,8 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("rng_bump", &rng_bump);
   m.impl("cond_request", &cond_request);
   m.impl("cond_partition", &cond_partition);
+  m.impl("pred_request", &pred_request);
+  m.impl("pred_mark", &pred_mark);
   m.impl("sim_prepare", &sim_prepare);
   m.impl("sim_sort", &sim_sort);
   m.impl("sim_w1", &sim_w1);

@@ -459,6 +459,52 @@ int cond_partition_workgroups(int rows);
 void launch_cond_partition(const CondPartitionArgs& a, hipStream_t stream);
 unsigned check_status_cond_gen();
 
+// Range and set predicates of a conditional request (kernels/cond_pred.hip), in device buffers like the request
+// itself: a range on a continuous column (lo <= x <= hi in the decoded space), a set on a categorical column (a
+// byte per label code).  A predicate may also drive: its span's options are then drawn by weight.
+constexpr int PRED_MAX = 16;        // predicates per request
+struct PredReq {
+  int n_pred;
+  const int* j;              // [n_pred] output column
+  const int* kind;           // [n_pred] 0: range, 1: set
+  const double* lo;          // [n_pred] inclusive bounds of a range (-inf / +inf: open)
+  const double* hi;
+  const int* lut_off;        // [n_pred] a set's first byte in lut
+  const int* lut_len;        // [n_pred] ... and its bytes: one per label code, 1 = allowed
+  const uint8_t* lut;        // [lut_total]
+  int lut_total;
+  int64_t* stats;            // [2 + PRED_MAX]: rows tested, rows rejected, first failures per predicate
+};
+struct PredRequestArgs {
+  const int* drv;            // [2]: the driving span, its output column
+  const int* drv_opt;        // [M] the span's options with positive weight, in option order
+  const double* drv_cum;     // [M] their cumulative normalised weights, drv_cum[M - 1] == 1.0
+  int M;
+  const int64_t* quota;      // [1]
+  const int64_t* filled;     // [1]
+  int rows;
+  int* col;                  // as CondRequestArgs
+  int* opt;
+  int* tgt;                  // [rows] 0 (-1: the quota is full)
+  float* h;
+  int ldh, cc, C;
+  const int* cond_off;
+  const int* cond_w;
+  int n_span;
+  uint64_t seed;
+  const uint64_t* rng_ctr;
+  uint32_t rng_stream;
+};
+void launch_pred_request(const PredRequestArgs& a, hipStream_t stream);
+struct PredMarkArgs {
+  PredReq p;
+  const double* out;         // [rows, n_cols] decoded pass
+  int rows, n_cols;
+  int* tgt;                  // [rows] -1 where a predicate fails
+};
+void launch_pred_mark(const PredMarkArgs& a, hipStream_t stream);
+unsigned check_status_cond_pred();
+
 // Similarity evaluator (kernels/similarity.hip): Avg_JSD / Avg_WD of a decoded table against a real one, on the
 // device.  Counting is in integers and every fp64 sum has a fixed order, so a table scores bit-identically on every
 // run; no launch allocates or waits on the host.

@@ -26,7 +26,11 @@ def main(argv=None):
                    help="only rows whose categorical column COL is VALUE (repeatable)")
     p.add_argument("-where_json", default=None,
                    help="the same as JSON; one column may map values to weights, e.g. "
-                        "'{\"class\": {\"back.\": 1, \"satan.\": 1}, \"protocol_type\": \"tcp\"}' (-n rows split by weight)")
+                        "'{\"class\": {\"back.\": 1, \"satan.\": 1}, \"protocol_type\": \"tcp\"}' (-n rows split by weight); "
+                        "a list of values means any of them, {\"min\": a, \"max\": b} a range on a continuous column")
+    p.add_argument("-where_range", action="append", default=[], metavar="COL=LO:HI",
+                   help="only rows whose continuous column COL lies in [LO, HI], in the units the CSV prints "
+                        "(repeatable; either side may be empty for an open bound)")
     p.add_argument("-max_passes", type=int, default=64, help="generation passes a conditional request may take")
     p.add_argument("-min_dcr", type=float, default=None, metavar="T",
                    help="privacy guard: write only rows farther than T from every real record, in the metric of "
@@ -88,7 +92,10 @@ def main(argv=None):
     import torch
     from fed_tgan_amd.models.conditional import parse_where
     from fed_tgan_amd.models.generator_io import load_generator
-    where = parse_where(args.where, args.where_json)
+    try:
+        where = parse_where(args.where, args.where_json, args.where_range)
+    except ValueError as e:
+        p.error(str(e))
     dev = torch.device("cuda", 0) if (torch.cuda.is_available() and args.backend != "torch") else torch.device("cpu")
     gen = load_generator(args.model, dev, backend=args.backend, seed=args.seed)
     out = args.out or f"{gen.name}_synthetic.csv"
@@ -114,6 +121,9 @@ def main(argv=None):
     if where:
         lc = gen.engine.last_conditional
         cond = f", {lc['passes']} passes, {lc['kept']} of {lc['generated']} generated rows accepted"
+        for pr in lc.get("predicates") or ():
+            cond += (f", {pr['predicate']} rejected {100.0 * pr['rejected'] / max(pr['tested'], 1):.1f} % of "
+                     f"{pr['tested']} rows")
     if args.min_dcr is not None:
         lg = gen.engine.last_guard
         cond += (f", guard min_dcr {args.min_dcr!r}: {lg['passes']} passes, {lg['rejected']} of {lg['generated']} "

@@ -32,7 +32,7 @@ class GenGraph:
 
 class GenerationMixin:
     def _init_generation(self):
-        self.gen_tables = self.gen_cond = None    # set_generation_tables
+        self.gen_tables = self.gen_cond = self.gen_counts = None    # set_generation_tables
         # _gen_bufs: (H, logits, col, opt) of the eager passes, grown on demand; _gen_graphs / _gen_split: n -> the
         # captured generate_decoded(n) / prep + body of generate_decoded_split(n); _cond_ent: (m, bins, fixed
         # columns) -> buffers / hipGraph of a conditional pass, _guard_ent: the same of a guarded pass; _gen_prepped:
@@ -65,6 +65,7 @@ class GenerationMixin:
                 codes = torch.as_tensor(np.asarray(m["i2s"], dtype=np.float64), device=dev)
                 cols.append((1, pos, w, -1, codes))
                 pos += w
+        self.gen_counts = np.asarray(cond.counts, dtype=np.float64)      # the span counts a driving range / set weighs
         self.gen_tables = {"cols": cols, "mu": torch.as_tensor(mu, dtype=torch.float64, device=dev),
                            "sd": torch.as_tensor(sd, dtype=torch.float64, device=dev)}
         self._drop_generation()
@@ -240,7 +241,15 @@ class GenerationMixin:
         same launches eagerly, and both give bit-identical tables from equal engine states.  Passes are issued in
         bursts that cannot overshoot (ceil(open quota / m) of them), with one readback of the filled counters per
         burst; max_passes passes without every quota full raise ConditionalSamplingError (no partial table).
-        ``self.last_conditional`` records passes, rows generated, rows kept and the per-value counts."""
+        ``self.last_conditional`` records passes, rows generated, rows kept and the per-value counts.
+
+        A request with range / set predicates (build_request) adds pred_mark after the decode: a row that fails a
+        predicate loses its target before the partition.  When a predicate drives, pred_request takes cond_request's
+        place (the driving span's options drawn by weight), the request has one bin, cond_partition compares no
+        value, and the rows come back in generation order.  Entries and captured passes are then also keyed by the
+        predicate shape (predicates, driver options, set-table bytes, whether a predicate drives);
+        ``last_conditional["predicates"]`` lists per predicate its column, the rows it tested and the rows whose
+        first failure it was, and a ConditionalSamplingError names the predicate with the most first failures."""
         from .conditional import ConditionalSamplingError
         if self.gen_tables is None:
             raise RuntimeError("set_generation_tables() first")
@@ -264,11 +273,13 @@ class GenerationMixin:
         else:       # a power of two with a quarter of slack for rejected rows: few distinct sizes to capture
             m = min(int(self.cfg.gen_chunk), max(1024, 1 << int(np.ceil(np.log2(max(1.25 * n, 1.0))))))
         self._wait_gen_done()
-        ent = self._cond_entry(m, nb, nf, n)
-        for k in ("drive", "bin_opt", "bin_code", "quota", "seg_off", "fixed_j", "fixed_code"):
+        ent = self._cond_entry(m, nb, nf, n, self._pred_shape(request))
+        for k in self._request_keys(ent):
             ent["req"][k].copy_(request[k])
         ent["req"]["filled"].zero_()
         ent["req"]["stats"].zero_()
+        if ent["P"]:
+            ent["req"]["pred_stats"].zero_()
         if use_graph and ent.get("graph") is None:
             self._capture_cond(ent, m)
         passes, filled = 0, [0] * nb
@@ -282,7 +293,8 @@ class GenerationMixin:
                     self.ops.check()
                 raise ConditionalSamplingError(
                     f"{passes} passes of {m} rows filled {sum(filled)} of {n} requested rows "
-                    f"(per value: {dict(zip(map(str, request['values']), filled))})", filled, quotas, request["values"])
+                    f"(per value: {dict(zip(map(str, request['values']), filled))})"
+                    f"{self._worst_predicate(self.last_conditional)}", filled, quotas, request["values"])
             burst = max(1, min(-(-open_rows // m), int(max_passes) - passes))
             for _ in range(burst):
                 if use_graph:
@@ -299,14 +311,75 @@ class GenerationMixin:
 
     def _cond_report(self, ent, request, passes, filled):
         st = ent["req"]["stats"].tolist()
-        return {"passes": int(passes), "generated": int(st[0]), "kept": int(st[1]), "filled": list(filled),
-                "values": list(request["values"])}
+        rep = {"passes": int(passes), "generated": int(st[0]), "kept": int(st[1]), "filled": list(filled),
+               "values": list(request["values"])}
+        if ent.get("P"):
+            # predicate k tests the rows its predecessors let through; "rejected": the rows whose first failure it is
+            from .conditional import describe_predicate
+            ps = ent["req"]["pred_stats"].tolist()
+            desc = list(request.get("predicates") or [])
+            tested, preds = int(ps[0]), []
+            for k in range(ent["P"]):
+                # (a hand-made request carries no description: its column index stands in)
+                col, text = (desc[k][0], describe_predicate(desc[k])) if k < len(desc) else \
+                    (int(request["pred_j"][k]), f"{k} on column {int(request['pred_j'][k])}")
+                preds.append({"column": col, "predicate": text, "tested": tested, "rejected": int(ps[2 + k])})
+                tested -= int(ps[2 + k])
+            rep["predicates"] = preds
+        return rep
 
-    def _cond_entry(self, m: int, nb: int, nf: int, n: int) -> dict:
-        """Static buffers of a conditional pass over m rows for requests of nb bins and nf fixed columns: the pass's
+    @staticmethod
+    def _worst_predicate(report) -> str:
+        """The clause of a ConditionalSamplingError that names the predicate with the most first failures."""
+        preds = (report or {}).get("predicates")
+        if not preds:
+            return ""
+        w = max(preds, key=lambda p: p["rejected"])
+        return (f"; the predicate {w['predicate']} rejected {w['rejected']} of the {w['tested']} rows it tested "
+                f"({100.0 * w['rejected'] / max(w['tested'], 1):.1f} %)")
+
+    @staticmethod
+    def _pred_shape(request) -> tuple:
+        """(predicates, driver options, bytes of the sets' tables, a predicate drives) of a request: with (m, bins,
+        fixed columns) the shape an entry's static buffers and its captured pass are made for."""
+        if request is None or "pred_j" not in request:
+            return (0, 0, 0, False)
+        drives = "drv" in request
+        return (int(request["pred_j"].numel()), int(request["drv_opt"].numel()) if drives else 0,
+                int(request["pred_lut"].numel()), drives)
+
+    @staticmethod
+    def _request_keys(ent) -> tuple:
+        """The request buffers copied into an entry's static ones."""
+        keys = ("drive", "bin_opt", "bin_code", "quota", "seg_off", "fixed_j", "fixed_code")
+        if ent["P"]:
+            keys += ("pred_j", "pred_kind", "pred_lo", "pred_hi", "pred_lut_off", "pred_lut_len", "pred_lut")
+        if ent["drives"]:
+            keys += ("drv", "drv_opt", "drv_cum")
+        return keys
+
+    def _pred_buffers(self, req: dict, pshape: tuple) -> None:
+        """The static predicate buffers of an entry (see _pred_shape), added to its request buffers."""
+        P, M, L, drives = pshape
+        dev = self.device
+        z = lambda k, dt: torch.zeros(k, dtype=dt, device=dev)      # noqa: E731
+        if P:
+            if P > getattr(self.ops, "PRED_MAX", 16):
+                raise ValueError(f"{P} predicates; the kernels' limit is {self.ops.PRED_MAX}")
+            req.update({"pred_j": z(P, torch.int32), "pred_kind": z(P, torch.int32), "pred_lo": z(P, torch.float64),
+                        "pred_hi": z(P, torch.float64), "pred_lut_off": z(P, torch.int32),
+                        "pred_lut_len": z(P, torch.int32), "pred_lut": z(L, torch.uint8),
+                        "pred_stats": z(2 + 16, torch.int64)})
+        if drives:
+            req.update({"drv": z(2, torch.int32), "drv_opt": z(M, torch.int32), "drv_cum": z(M, torch.float64)})
+
+    def _cond_entry(self, m: int, nb: int, nf: int, n: int, pshape: tuple = (0, 0, 0, False)) -> dict:
+        """Static buffers of a conditional pass over m rows for requests of nb bins and nf fixed columns (and
+        ``pshape``, _pred_shape: predicates, driver options, set-table bytes, whether a predicate drives): the pass's
         activations / logits / conditions / targets / decoded rows, the request buffers the launches read, and the
         quota segments (grown, and the graph dropped, when a request asks for more rows)."""
-        key = (m, nb, nf)
+        pshape = tuple(pshape)
+        key = (m, nb, nf) if pshape == (0, 0, 0, False) else (m, nb, nf) + pshape
         ent = self._cond_ent.get(key)
         dev = self.device
         if ent is None:
@@ -318,7 +391,8 @@ class GenerationMixin:
                    "req": {"drive": i32(2), "bin_opt": i32(nb), "bin_code": f64(nb), "quota": i64(nb),
                            "filled": i64(nb), "seg_off": i64(nb), "fixed_j": i32(nf), "fixed_code": f64(nf),
                            "stats": i64(2)},
-                   "dst": None, "graph": None}
+                   "P": pshape[0], "drives": bool(pshape[3]), "dst": None, "graph": None}
+            self._pred_buffers(ent["req"], pshape)
             self._cond_ent[key] = ent
         if ent["dst"] is None or ent["dst"].shape[0] < n:
             if ent["graph"] is not None:
@@ -333,11 +407,20 @@ class GenerationMixin:
         w16 = self._gen_weights16() if self.gen16 else None
         o.sample_gen(self.gen_cond, H, self.c_cols, self.z_cols, col_out=col, opt_out=opt, stream_id=21)
         # (stream 24: the request's own Philox stream; 21-23 are the generation sampler's, activation's and decode's)
-        o.cond_request(req, col, opt, tgt, self.gen_cond, h=None if w16 is not None else H, c_col0=self.c_cols[0],
-                       stream_id=24)
+        if ent["drives"]:   # (stream 25: the weighted draw of a driving range / set)
+            o.pred_request(req, col, opt, tgt, self.gen_cond, h=None if w16 is not None else H, c_col0=self.c_cols[0],
+                           stream_id=25)
+        else:
+            o.cond_request(req, col, opt, tgt, self.gen_cond, h=None if w16 is not None else H,
+                           c_col0=self.c_cols[0], stream_id=24)
         self._gen_forward(H, lg, col, opt, w16)
         o.sample_decode(lg, ent["out"], self.gen_tables, stream_id=23)
-        o.cond_partition(req, ent["out"], tgt, ent["dst"])
+        if ent["P"]:
+            o.pred_mark(req, ent["out"], tgt)
+        if ent["drives"]:
+            o.cond_partition(req, ent["out"], tgt, ent["dst"], any_value=True)
+        else:
+            o.cond_partition(req, ent["out"], tgt, ent["dst"])
 
     def _capture_cond(self, ent: dict, m: int):
         """Capture one conditional pass.  The warm-up sizes every lazily built table and scratch buffer; the RNG and the
@@ -348,6 +431,8 @@ class GenerationMixin:
             ctr.copy_(ctr0)
             req["filled"].zero_()
             req["stats"].zero_()
+            if ent["P"]:
+                req["pred_stats"].zero_()
         run = partial(self._cond_pass, ent, m)
         ent["graph"], = warm_and_capture(self.device, run, [run], snapshot=ctr.clone, restore=restore,
                                          mode=self.capture_mode)
@@ -370,7 +455,12 @@ class GenerationMixin:
         counter and the counters restored after the warm-up, so eager and replayed runs from equal states give
         bit-identical tables.  max_passes passes without n rows raise ConditionalSamplingError (no table; the message
         carries the rejected share).  ``self.last_guard`` = {"passes", "generated", "rejected", "kept"}; with a
-        request ``self.last_conditional`` is set as generate_decoded_where sets it."""
+        request ``self.last_conditional`` is set as generate_decoded_where sets it.
+
+        A request with range / set predicates runs pred_mark between the decode and the guard's steps (and
+        pred_request in cond_request's place when a predicate drives).  The radius test still covers every row of the
+        pass, so ``rejected`` counts every row within the radius, including rows a predicate had already rejected:
+        it stays the guard's own rate over ``generated``, whatever the predicates let through."""
         from .conditional import ConditionalSamplingError
         if self.gen_tables is None:
             raise RuntimeError("set_generation_tables() first")
@@ -404,15 +494,17 @@ class GenerationMixin:
         else:
             m = min(int(self.cfg.gen_chunk), max(1024, 1 << int(np.ceil(np.log2(max(1.25 * n, 1.0))))))
         self._wait_gen_done()
-        ent = self._guard_entry(m, nb, nf, n, guard, request is not None)
+        ent = self._guard_entry(m, nb, nf, n, guard, request is not None, self._pred_shape(request))
         req = ent["req"]
         if request is not None:
-            for k in ("drive", "bin_opt", "bin_code", "quota", "seg_off", "fixed_j", "fixed_code"):
+            for k in self._request_keys(ent):
                 req[k].copy_(request[k])
         else:
             req["quota"].fill_(n)
         req["filled"].zero_()
         req["stats"].zero_()
+        if ent["P"]:
+            req["pred_stats"].zero_()
         ent["gstats"].zero_()
         if use_graph and ent.get("graph") is None:
             self._capture_guard(ent, m)
@@ -437,7 +529,8 @@ class GenerationMixin:
                 raise ConditionalSamplingError(
                     f"{passes} passes of {m} rows delivered {sum(filled)} of {n} rows; the guard (min_dcr "
                     f"{guard.min_dcr!r}) rejected {lg['rejected']} of {lg['generated']} generated rows "
-                    f"({100.0 * share:.1f} %)", filled, quotas, values)
+                    f"({100.0 * share:.1f} %){self._worst_predicate(self.last_conditional if request else None)}",
+                    filled, quotas, values)
             burst = max(1, min(-(-open_rows // m), int(max_passes) - passes))
             for _ in range(burst):
                 if use_graph:
@@ -452,7 +545,8 @@ class GenerationMixin:
             self.ops.check()
         return out
 
-    def _guard_entry(self, m: int, nb: int, nf: int, n: int, guard, with_request: bool) -> dict:
+    def _guard_entry(self, m: int, nb: int, nf: int, n: int, guard, with_request: bool,
+                     pshape: tuple = (0, 0, 0, False)) -> dict:
         """_cond_entry's buffers plus the guard's (packed pass, near, the search's scratch, its two counters), per
         (m, bins, fixed columns, request or not) of one guard: a captured pass reads the guard's tables, so another
         guard starts afresh."""
@@ -461,7 +555,8 @@ class GenerationMixin:
             if dev.type == "cuda":
                 torch.cuda.synchronize(dev)
             self._guard_ent = {}
-        key = (m, nb, nf, bool(with_request))
+        pshape = tuple(pshape)
+        key = (m, nb, nf, bool(with_request)) + (() if pshape == (0, 0, 0, False) else pshape)
         ent = self._guard_ent.get(key)
         if ent is None:
             H, lg, col, opt = self._gen_alloc(m, self.gen16)
@@ -473,7 +568,8 @@ class GenerationMixin:
                            "filled": i64(nb), "seg_off": i64(nb), "fixed_j": i32(nf), "fixed_code": f64(nf),
                            "stats": i64(2)},
                    "guard": guard, "gbufs": guard.buffers(m), "gstats": i64(2), "request": bool(with_request),
-                   "dst": None, "graph": None}
+                   "P": pshape[0], "drives": bool(pshape[3]), "dst": None, "graph": None}
+            self._pred_buffers(ent["req"], pshape)
             self._guard_ent[key] = ent
         if ent["dst"] is None or ent["dst"].shape[0] < n:
             if ent["graph"] is not None:
@@ -487,16 +583,21 @@ class GenerationMixin:
         H, lg, col, opt, tgt = ent["H"], ent["lg"], ent["col"], ent["opt"], ent["tgt"]
         w16 = self._gen_weights16() if self.gen16 else None
         o.sample_gen(self.gen_cond, H, self.c_cols, self.z_cols, col_out=col, opt_out=opt, stream_id=21)
-        if ent["request"]:
+        if ent["drives"]:
+            o.pred_request(req, col, opt, tgt, self.gen_cond, h=None if w16 is not None else H, c_col0=self.c_cols[0],
+                           stream_id=25)
+        elif ent["request"]:
             o.cond_request(req, col, opt, tgt, self.gen_cond, h=None if w16 is not None else H, c_col0=self.c_cols[0],
                            stream_id=24)
         else:
             tgt.zero_()         # every row aims at the one bin
         self._gen_forward(H, lg, col, opt, w16)
         o.sample_decode(lg, ent["out"], self.gen_tables, stream_id=23)
+        if ent["P"]:
+            o.pred_mark(req, ent["out"], tgt)
         guard.launch(ent["out"], *ent["gbufs"])
         o.guard_mark(ent["gbufs"][2], tgt, ent["gstats"])
-        o.cond_partition(req, ent["out"], tgt, ent["dst"], any_value=not ent["request"])
+        o.cond_partition(req, ent["out"], tgt, ent["dst"], any_value=ent["drives"] or not ent["request"])
 
     def _capture_guard(self, ent: dict, m: int):
         """Capture one guarded pass; the RNG counter, the request's and the guard's counters are put back after the
@@ -508,6 +609,8 @@ class GenerationMixin:
             req["filled"].zero_()
             req["stats"].zero_()
             ent["gstats"].zero_()
+            if ent["P"]:
+                req["pred_stats"].zero_()
         run = partial(self._guard_pass, ent, m)
         ent["graph"], = warm_and_capture(self.device, run, [run], snapshot=ctr.clone, restore=restore,
                                          mode=self.capture_mode)

@@ -67,7 +67,11 @@ class LoadedGenerator:
 
         where ({column name: value | {value: weight}}, models/conditional.py): exactly n rows carrying the
         requested category values, grouped by the weighted column's values in request order; raises
-        ConditionalSamplingError when max_passes generation passes do not fill the request.
+        ConditionalSamplingError when max_passes generation passes do not fill the request.  A categorical column
+        also takes a list of values (any of them, in the model's own proportions) and a continuous one
+        {"min": a, "max": b} in the units the CSV prints (either key may be absent; inclusive, enforced on the decoded
+        value); when such an entry comes first and no column carries weights it drives, and the rows come back in
+        generation order.
 
         min_dcr (a float >= 0) with guard_real (the real table: a DataFrame or a CSV path): the privacy guard
         (eval/privacy.py PrivacyGuard) -- no returned row lies within distance min_dcr of a real record, in the
@@ -308,13 +312,15 @@ class LoadedGenerator:
             req = None
             if where:
                 from .conditional import build_request
-                req = build_request(self.transformer, self.meta, self.vocabs, where, int(n), self.engine.device)
+                req = build_request(self.transformer, self.meta, self.vocabs, where, int(n), self.engine.device,
+                                    counts=self.engine.gen_counts)
             return self.engine.generate_decoded_guarded(int(n), guard, request=req, max_passes=max_passes)
         if guard_real is not None:
             raise ValueError("guard_real without min_dcr: give the radius (0 keeps out exact copies)")
         if where:
             from .conditional import build_request
-            req = build_request(self.transformer, self.meta, self.vocabs, where, int(n), self.engine.device)
+            req = build_request(self.transformer, self.meta, self.vocabs, where, int(n), self.engine.device,
+                                    counts=self.engine.gen_counts)
             return self.engine.generate_decoded_where(int(n), req, max_passes=max_passes)
         return self.engine.generate_decoded(int(n))
 

@@ -79,10 +79,13 @@ class CTGANSynthesizer(BaseSynthesizer):
         """Decoded rows (continuous values and categorical labels as in ``transformer.inverse_transform``).
 
         where ({column index: category value | {category value: weight}}, raw values as in the training data; see
-        models/conditional.py): exactly n rows carrying those values, grouped by the weighted column's values."""
+        models/conditional.py): exactly n rows carrying those values, grouped by the weighted column's values.  A
+        categorical column also takes a list of values (any of them), a continuous one {"min": a, "max": b} in the
+        model's decoded space; when such an entry drives, the rows come back in generation order."""
         if where:
             from .conditional import request_from_codes
-            req = request_from_codes(self.transformer, [(int(j), v) for j, v in where.items()], int(n), self.device)
+            req = request_from_codes(self.transformer, [(int(j), v) for j, v in where.items()], int(n), self.device,
+                                     counts=self.engine.gen_counts)
             return self.engine.generate_decoded_where(int(n), req, max_passes=max_passes).cpu().numpy()
         return self.engine.generate_decoded(n).cpu().numpy()
 

@@ -601,6 +601,20 @@ class HipOps:
         else:
             self.L.cond_partition(*self._cond_req(req), out, tgt, dst, sc[0], sc[1])
 
+    PRED_MAX = 16          # kernels/launch.h PRED_MAX
+
+    def pred_request(self, req, col, opt, tgt, cond, h=None, c_col0=0, stream_id=25, ctr=None):
+        """Same contract as TorchOps.pred_request (kernels/cond_pred.hip pred_request_kernel); the draw is keyed on
+        (seed, stream_id, step counter, row), with cond_request's words and double."""
+        self.L.pred_request(req["drv"], req["drv_opt"], req["drv_cum"], req["quota"], req["filled"], col, opt, tgt, h,
+                            int(c_col0), cond["cond_offset"], cond["cond_width"], self.seed,
+                            self.ctr if ctr is None else ctr, int(stream_id) * 16)
+
+    def pred_mark(self, req, out, tgt):
+        """Same contract (and bit-identical results) as TorchOps.pred_mark (kernels/cond_pred.hip pred_mark_kernel)."""
+        self.L.pred_mark(req["pred_j"], req["pred_kind"], req["pred_lo"], req["pred_hi"], req["pred_lut_off"],
+                         req["pred_lut_len"], req["pred_lut"], req["pred_stats"], out, tgt)
+
     # ------------------------------------------------------------------ similarity evaluator
     SIM_SORT_TILE = 2048   # kernels/launch.h SIM_SORT_TILE: keys per sorted LDS tile / merged output tile
 

@@ -422,6 +422,84 @@ class TorchOps:
         req["stats"][0] += m
         req["stats"][1] += int(keep.sum())
 
+    PRED_MAX = 16          # predicates per request (kernels/launch.h PRED_MAX)
+
+    def pred_request(self, req, col, opt, tgt, cond, h=None, c_col0=0, stream_id=25):
+        """cond_request for a request whose driver is a range or a set (models/conditional.py): one bin, and the
+        options of the driving span drawn by weight.
+
+        req: the request dict with drv int32 [2] (cond-span index, output column), drv_opt int32 [M] (the span's
+        options with positive weight, in option order), drv_cum float64 [M] (their cumulative normalised weights,
+        drv_cum[M - 1] == 1.0) and quota / filled int64 [1].  Row b draws u in (0, 1] and takes k = the number of
+        entries with drv_cum[i] <= u, clamped to M - 1; col[b] = drv[0], opt[b] = drv_opt[k], tgt[b] = 0, and the
+        hot element of h moves as in cond_request.  quota[0] - filled[0] <= 0: tgt = -1, col / opt / h untouched.
+        A driver outside the span tables leaves the rows without a target."""
+        m = tgt.shape[0]
+        if int(req["quota"][0]) - int(req["filled"][0]) <= 0:
+            tgt.fill_(-1)
+            return
+        cum = req["drv_cum"]
+        u = torch.rand(m, dtype=torch.float64, device=tgt.device)
+        k = torch.searchsorted(cum, u, right=True).clamp_(max=cum.numel() - 1)
+        span = int(req["drv"][0])
+        o = req["drv_opt"].long()[k]
+        width = cond["cond_width"].long()
+        if not 0 <= span < width.numel() or bool(((o < 0) | (o >= width[span])).any()):
+            tgt.fill_(-1)
+            return
+        if h is not None:
+            rows = torch.arange(m, device=tgt.device)
+            off = cond["cond_offset"].long()
+            h[rows, c_col0 + off[col[:m].long()] + opt[:m].long()] = 0.0
+            h[rows, c_col0 + off[span] + o] = 1.0
+        col[:m] = span
+        opt[:m] = o.to(opt.dtype)
+        tgt.zero_()
+
+    def pred_mark(self, req, out, tgt):
+        """Test the rows of a decoded pass against a request's predicates, after the decode and before any guard
+        step and cond_partition.
+
+        req: pred_j / pred_kind int32 [P] (output column; 0 range, 1 set), pred_lo / pred_hi float64 [P],
+        pred_lut_off / pred_lut_len int32 [P], pred_lut uint8 (one byte per label code, 1 = allowed), pred_stats
+        int64 [2 + PRED_MAX].  A row with tgt[r] < 0 is left alone and not counted.  Any other row is tested in
+        request order: a range passes iff lo <= v <= hi (NaN fails), a set iff v == trunc(v), 0 <= v < lut_len and
+        pred_lut[lut_off + int(v)] != 0; a predicate whose column or table slice lies outside its buffer fails.  The
+        first failing predicate k sets tgt[r] = -1.  pred_stats[0] += rows tested, [1] += rows rejected, [2 + k] +=
+        rows whose first failure is predicate k."""
+        P = int(req["pred_j"].numel())
+        if P > self.PRED_MAX:
+            raise ValueError(f"{P} predicates; the limit is {self.PRED_MAX}")
+        m = out.shape[0]
+        if P == 0 or m == 0:
+            return
+        t = tgt[:m]
+        live = t >= 0
+        first = torch.full((m,), -1, dtype=torch.long, device=out.device)
+        lut = req["pred_lut"]
+        rows = zip(req["pred_j"].tolist(), req["pred_kind"].tolist(), req["pred_lo"].tolist(),
+                   req["pred_hi"].tolist(), req["pred_lut_off"].tolist(), req["pred_lut_len"].tolist())
+        for k, (j, kind, lo, hi, off, ln) in enumerate(rows):
+            if not 0 <= j < out.shape[1]:
+                ok = torch.zeros(m, dtype=torch.bool, device=out.device)
+            elif kind == 0:
+                v = out[:, j]
+                ok = (v >= lo) & (v <= hi)
+            elif off < 0 or ln < 0 or off + ln > lut.numel():
+                ok = torch.zeros(m, dtype=torch.bool, device=out.device)
+            else:
+                v = out[:, j]
+                ok = (v == torch.trunc(v)) & (v >= 0) & (v < ln)
+                idx = torch.where(ok, v, torch.zeros_like(v)).long() + off
+                ok &= lut[idx.clamp_(0, max(lut.numel() - 1, 0))] != 0 if lut.numel() else False
+            first = torch.where(live & (first < 0) & ~ok, torch.full_like(first, k), first)
+        rej = first >= 0
+        t[rej] = -1
+        st = req["pred_stats"]
+        st[0] += int(live.sum())
+        st[1] += int(rej.sum())
+        st[2:2 + P] += torch.bincount(first[rej], minlength=P).to(st.dtype)
+
     # ------------------------------------------------------------------ similarity evaluator
     SIM_SORT_TILE = 2048   # the HIP sort's tile; no meaning here beyond the shared attribute
     SIM_PLAIN, SIM_NONNEG, SIM_CAT = 0, 1, 2
