@@ -1390,6 +1390,52 @@ void guard_mark(const Tensor& near, const Tensor& tgt, const Tensor& stats) {
                              cur_stream());
 }
 
+namespace {
+bool nn_offsets(const Tensor& t, int64_t k) {
+  return t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous() && t.numel() == k;
+}
+}  // namespace
+
+void nn_merge_shards(const Tensor& parts, const Tensor& offsets, const Tensor& d1, const Tensor& d2, const Tensor& i1,
+                     const Tensor& owner, const Tensor& by_client) {
+  TORCH_CHECK(sim_f64(parts) && parts.dim() == 3 && parts.size(2) == 3,
+              "nn_merge_shards: parts must be contiguous float64 [K, n, 3]");
+  const int64_t k = parts.size(0), n = parts.size(1);
+  TORCH_CHECK(k >= 1 && k <= fedtgan::NN_MAX_SHARDS, "nn_merge_shards: 1..", fedtgan::NN_MAX_SHARDS, " shards, got ",
+              k);
+  TORCH_CHECK(n < (int64_t)INT32_MAX / 3, "nn_merge_shards: too many rows");
+  TORCH_CHECK(nn_offsets(offsets, k), "nn_merge_shards: offsets int64 [K] on the device");
+  TORCH_CHECK(sim_f64(d1) && sim_f64(d2) && sim_i32(i1) && sim_i32(owner) && d1.numel() >= n && d2.numel() >= n &&
+                  i1.numel() >= n && owner.numel() >= n,
+              "nn_merge_shards: d1 / d2 float64 and i1 / owner int32, one entry per row");
+  TORCH_CHECK(by_client.is_cuda() && by_client.scalar_type() == at::kLong && by_client.is_contiguous() &&
+                  by_client.numel() == 2 * k, "nn_merge_shards: by_client int64 [2, K]");
+  fedtgan::NnMergeShardsArgs a{};
+  a.parts = parts.data_ptr<double>();
+  a.offsets = offsets.data_ptr<int64_t>();
+  a.k = (int)k;
+  a.n = (int)n;
+  a.d1 = d1.data_ptr<double>();
+  a.d2 = d2.data_ptr<double>();
+  a.i1 = i1.data_ptr<int>();
+  a.owner = owner.data_ptr<int>();
+  a.by_client = (unsigned long long*)by_client.data_ptr<int64_t>();
+  fedtgan::launch_nn_merge_shards(a, cur_stream());
+}
+
+void nn_within_merge_shards(const Tensor& near, const Tensor& offsets, const Tensor& near_out, const Tensor& owner) {
+  TORCH_CHECK(sim_i32(near) && near.dim() == 2, "nn_within_merge_shards: near must be contiguous int32 [K, n]");
+  const int64_t k = near.size(0), n = near.size(1);
+  TORCH_CHECK(k >= 1 && k <= fedtgan::NN_MAX_SHARDS, "nn_within_merge_shards: 1..", fedtgan::NN_MAX_SHARDS,
+              " shards, got ", k);
+  TORCH_CHECK(n < (int64_t)INT32_MAX, "nn_within_merge_shards: too many rows");
+  TORCH_CHECK(nn_offsets(offsets, k), "nn_within_merge_shards: offsets int64 [K] on the device");
+  TORCH_CHECK(sim_i32(near_out) && sim_i32(owner) && near_out.numel() >= n && owner.numel() >= n,
+              "nn_within_merge_shards: near_out / owner int32, one entry per row");
+  fedtgan::launch_nn_within_merge_shards(near.data_ptr<int>(), offsets.data_ptr<int64_t>(), (int)k, (int)n,
+                                         near_out.data_ptr<int>(), owner.data_ptr<int>(), cur_stream());
+}
+
 void nn_stats(const Tensor& d1, const Tensor& d2, int64_t n, const Tensor& keys, const Tensor& part) {
   TORCH_CHECK(sim_f64(d1) && sim_f64(d2) && n >= 1 && n < (int64_t)INT32_MAX && d1.numel() >= n && d2.numel() >= n,
               "nn_stats: d1 / d2 float64 with n >= 1 entries");
@@ -2483,6 +2529,10 @@ TORCH_LIBRARY(fedtgan, m) {
       "nn_within(Tensor q_cont, Tensor q_cat, Tensor r_cont, Tensor r_cat, Tensor t2, Tensor(a!) near, "
       "Tensor(b!) scratch) -> ()");
   m.def("guard_mark(Tensor near, Tensor(a!) tgt, Tensor(b!) stats) -> ()");
+  m.def(
+      "nn_merge_shards(Tensor parts, Tensor offsets, Tensor(a!) d1, Tensor(b!) d2, Tensor(c!) i1, Tensor(d!) owner, "
+      "Tensor(e!) by_client) -> ()");
+  m.def("nn_within_merge_shards(Tensor near, Tensor offsets, Tensor(a!) near_out, Tensor(b!) owner) -> ()");
   m.def("nn_stats(Tensor d1, Tensor d2, int n, Tensor(a!) keys, Tensor(b!) part) -> ()");
   m.def("nn_percentiles(Tensor keys, int n, Tensor part, Tensor(a!) out) -> ()");
   m.def("nn_query_tile() -> int", &nn_query_tile);
@@ -2623,6 +2673,8 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("nn_top2", &nn_top2);
   m.impl("nn_within", &nn_within);
   m.impl("guard_mark", &guard_mark);
+  m.impl("nn_merge_shards", &nn_merge_shards);
+  m.impl("nn_within_merge_shards", &nn_within_merge_shards);
   m.impl("nn_stats", &nn_stats);
   m.impl("nn_percentiles", &nn_percentiles);
   m.impl("nn_topk", &nn_topk);

@@ -600,6 +600,22 @@ struct NnWithinArgs {
 void launch_nn_within(NnWithinArgs a, hipStream_t stream);
 // tgt[i] = -1 where near[i] >= 0; stats[0] += n, stats[1] += rows with near >= 0
 void launch_guard_mark(const int* near, int* tgt, int n, int64_t* stats, hipStream_t stream);
+// Federated audit / guard (eval/fed_privacy.py): the answers of K shards folded into the answer over their union.
+constexpr int NN_MAX_SHARDS = 64;     // shards one merge folds (a thread walks them in order)
+struct NnMergeShardsArgs {
+  const double* parts;    // [k, n, 3]: shard s's (d1, d2, i1 as fp64; -1: no candidate) per query row
+  const int64_t* offsets; // [k] exclusive prefix sums of the shard row counts
+  int k, n;
+  double* d1;             // [n] the two smallest distances over the union, with multiplicity
+  double* d2;
+  int* i1;                // [n] offsets[s] + local of the lowest global index at d1, -1: none
+  int* owner;             // [n] that s, -1: none
+  unsigned long long* by_client;   // [2, k], overwritten: rows nearest to shard s; rows shard s holds a copy of
+};
+void launch_nn_merge_shards(const NnMergeShardsArgs& a, hipStream_t stream);
+// near [k, n]: shard s's lowest local hit or -1 -> near_out[n] = offsets[s] + near[s] of the first shard with a hit
+void launch_nn_within_merge_shards(const int* near, const int64_t* offsets, int k, int n, int* near_out, int* owner,
+                                   hipStream_t stream);
 int nn_stats_blocks(int64_t n);
 // keys [2, ld]: sqrt(d1) and the ratio sqrt(d1 / d2) of rows [0, n); part [2 * nn_stats_blocks(n)]
 void launch_nn_stats(const double* d1, const double* d2, int n, double* keys, int64_t ld, double* part,

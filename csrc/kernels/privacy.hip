@@ -9,6 +9,8 @@
 //  nn_within_kernel       the privacy guard's radius test on the same grid: the lowest reference row with d2 <= t2 per
 //                         (query, chunk), candidates abandoned once out of range; nn_within_merge_kernel takes the
 //                         first chunk with a hit, guard_mark_kernel clears the target of the rows that have one
+//  nn_merge_shards_kernel the (d1, d2, i1) answers of K shards folded in client order into the answer over their union,
+//                         with per-client counts; nn_within_merge_shards_kernel the same for the radius test
 //  nn_stats_kernel        sqrt(d1) and the distance ratio into two key rows (sorted by launch_sim_sort afterwards);
 //                         per-workgroup minimum and count of exact zeros in fixed slots
 //  nn_percentile_kernel   the two interpolated 5th percentiles from the sorted rows, the minimum and the share of zeros
@@ -429,6 +431,101 @@ void launch_guard_mark(const int* near, int* tgt, int n, int64_t* stats, hipStre
   if (n == 0) return;
   hipLaunchKernelGGL(guard_mark_kernel, dim3((unsigned)((n + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS), 0,
                      stream, near, tgt, n, (unsigned long long*)stats);
+}
+
+// ============================================================================ shard merges (eval/fed_privacy.py)
+// The answers of K shards over the same query rows folded into the answer over the union of the shards.  One thread
+// per query row walks the shards in client order exactly as nn_merge_kernel walks chunks: strict <, so the lowest
+// global index wins a tie, and a shard's second distance competes with the others' first (two shards holding a copy
+// each give d1 = d2 = 0).  A shard without a candidate carries d1 = +inf and wins nothing.  A thread reads its row's
+// three doubles, so a wave reads 64 x 24 contiguous bytes per shard.  by_client: per-wave ballots into LDS counters,
+// then one integer atomic per (workgroup, shard) with a non-zero count: the sums do not depend on workgroup order.
+__global__ __launch_bounds__(NN_THREADS) void nn_merge_shards_kernel(NnMergeShardsArgs a) {
+  __shared__ int cnt[2 * NN_MAX_SHARDS];
+  const int tid = threadIdx.x;
+  const int q = blockIdx.x * NN_THREADS + tid;
+  const bool live = q < a.n;
+  const bool lead = (tid & (WAVE - 1)) == 0;
+  if (tid < 2 * NN_MAX_SHARDS) cnt[tid] = 0;
+  __syncthreads();
+  double d1 = nn_inf(), d2 = nn_inf();
+  int i1 = -1, owner = -1;
+  for (int s = 0; s < a.k; ++s) {                 // (uniform: every thread of a wave reaches the ballot)
+    double b1 = nn_inf(), b2 = nn_inf(), bi = -1.0;
+    if (live) {
+      const double* p = a.parts + ((size_t)s * a.n + q) * 3;
+      b1 = p[0];
+      b2 = p[1];
+      bi = p[2];
+    }
+    if (b1 < d1 && bi >= 0.0) {
+      d2 = b2 < d1 ? b2 : d1;
+      d1 = b1;
+      i1 = (int)(a.offsets[s] + (long long)bi);
+      owner = s;
+    } else if (b1 < d2) {
+      d2 = b1;
+    }
+    const unsigned long long copies = __ballot(live && b1 == 0.0);
+    if (lead && copies) atomicAdd(&cnt[NN_MAX_SHARDS + s], __popcll(copies));
+  }
+  for (int s = 0; s < a.k; ++s) {
+    const unsigned long long mine = __ballot(owner == s);
+    if (lead && mine) atomicAdd(&cnt[s], __popcll(mine));
+  }
+  if (live) {
+    a.d1[q] = d1;
+    a.d2[q] = d2;
+    a.i1[q] = i1;
+    a.owner[q] = owner;
+  }
+  __syncthreads();
+  if (tid < 2 * NN_MAX_SHARDS) {
+    const int row = tid / NN_MAX_SHARDS, s = tid - row * NN_MAX_SHARDS;
+    if (s < a.k && cnt[tid]) atomicAdd(&a.by_client[(size_t)row * a.k + s], (unsigned long long)cnt[tid]);
+  }
+}
+
+// (a kernel, not a memset: in a captured pass the counters are cleared by a kernel node ahead of the merge's)
+__global__ __launch_bounds__(2 * NN_MAX_SHARDS) void nn_clear_counts_kernel(unsigned long long* by_client, int slots) {
+  if ((int)threadIdx.x < slots) by_client[threadIdx.x] = 0ull;
+}
+
+void launch_nn_merge_shards(const NnMergeShardsArgs& a, hipStream_t stream) {
+  require_unbatched("nn_merge_shards");
+  if (a.k < 1 || a.k > NN_MAX_SHARDS) throw std::runtime_error("nn_merge_shards: 1..64 shards");
+  if (a.n < 0) throw std::runtime_error("nn_merge_shards: row count");
+  hipLaunchKernelGGL(nn_clear_counts_kernel, dim3(1), dim3(2 * NN_MAX_SHARDS), 0, stream, a.by_client, 2 * a.k);
+  if (a.n == 0) return;
+  hipLaunchKernelGGL(nn_merge_shards_kernel, dim3((unsigned)((a.n + NN_THREADS - 1) / NN_THREADS)), dim3(NN_THREADS),
+                     0, stream, a);
+}
+
+// the shards hold ascending ranges of the global index: the first shard with a hit has the lowest
+__global__ __launch_bounds__(NN_THREADS) void nn_within_merge_shards_kernel(const int* near, const int64_t* offsets,
+                                                                            int k, int n, int* near_out, int* owner) {
+  const int q = blockIdx.x * NN_THREADS + threadIdx.x;
+  if (q >= n) return;
+  int hit = -1, own = -1;
+  for (int s = 0; s < k && own < 0; ++s) {
+    const int h = near[(size_t)s * n + q];
+    if (h >= 0) {
+      hit = (int)(offsets[s] + (long long)h);
+      own = s;
+    }
+  }
+  near_out[q] = hit;
+  owner[q] = own;
+}
+
+void launch_nn_within_merge_shards(const int* near, const int64_t* offsets, int k, int n, int* near_out, int* owner,
+                                   hipStream_t stream) {
+  require_unbatched("nn_within_merge_shards");
+  if (k < 1 || k > NN_MAX_SHARDS) throw std::runtime_error("nn_within_merge_shards: 1..64 shards");
+  if (n < 0) throw std::runtime_error("nn_within_merge_shards: row count");
+  if (n == 0) return;
+  hipLaunchKernelGGL(nn_within_merge_shards_kernel, dim3((unsigned)((n + NN_THREADS - 1) / NN_THREADS)),
+                     dim3(NN_THREADS), 0, stream, near, offsets, k, n, near_out, owner);
 }
 
 // ============================================================================ table scores

@@ -110,6 +110,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "{name}_result/similarity_online.csv); 0 = off")
     p.add_argument("-eval_real", type=str, default=None,
                    help="the real table's CSV for -eval_every (default: the clients' synthetic shards, rebuilt)")
+    p.add_argument("-privacy_every", type=int, default=0,
+                   help="federated privacy audit: DCR / NNDR of every N-th round's table against every client's own "
+                        "records, which stay where they are (-> the metrics log and {name}_result/privacy_online.csv); "
+                        "0 = off")
+    p.add_argument("-min_dcr", type=float, default=None,
+                   help="federated privacy guard: after the last round write {name}_result/{name}_guarded.csv, rows "
+                        "none of which lies within this DCR of any client's record (0 keeps out exact copies)")
+    p.add_argument("-guard_rows", type=int, default=None, help="rows of the guarded table (default: -n_sample)")
+    p.add_argument("-guard_max_passes", type=int, default=64,
+                   help="give up after this many generation passes of the guarded table")
     p.add_argument("-quiet", action="store_true")
     return p
 
@@ -144,7 +154,8 @@ def fed_config_from_args(args):
                      dump_real=args.dump_real, async_csv=not args.sync_csv, init=args.init,
                      batched_clients=args.batched_clients, table_reader=args.table_reader,
                      pipeline_sample={"auto": None, "on": True, "off": False}[args.pipeline_sample],
-                     eval_every=args.eval_every, eval_real=args.eval_real)
+                     eval_every=args.eval_every, eval_real=args.eval_real, privacy_every=args.privacy_every,
+                     min_dcr=args.min_dcr, guard_rows=args.guard_rows, guard_max_passes=args.guard_max_passes)
 
 
 def pick_device(rank: int, colocated: bool, backend: str, mode: str = "fedavg") -> torch.device:
@@ -269,6 +280,14 @@ def main(argv: Optional[List[str]] = None) -> None:
                                  args.world_size):
             parser.error("-eval_every with -datapath needs -eval_real: the federator cannot rebuild tables the "
                          "clients read from their own CSVs")
+    if args.privacy_every > 0 or args.min_dcr is not None:
+        from .fed.audit import refuse_unsupported
+        try:
+            refuse_unsupported(fed_config_from_args(args))
+        except ValueError as e:
+            parser.error(str(e))
+        if args.local_clients and (args.world_size > 1 or args.rank is not None):
+            parser.error("-privacy_every / -min_dcr: not supported with -world_size N -local_clients K together")
     if args.local_clients:
         if args.mode == "mdgan":
             raise SystemExit("-local_clients: the MD-GAN split mode runs one client per process")

@@ -94,8 +94,11 @@ def code_real_table(real: pd.DataFrame, meta: dict, vocabs: Sequence) -> np.ndar
 
 class DevicePrivacy(DeviceEvaluator):
     def __init__(self, real, meta: dict, vocabs: Sequence, device, ops=None, max_rows: int = 40000,
-                 baseline: bool = True, graph: bool = False):
-        """real: the real table as a DataFrame, or already coded as a float64 [m, n_cols] array."""
+                 baseline: bool = True, graph: bool = False, bounds=None):
+        """real: the real table as a DataFrame, or already coded as a float64 [m, n_cols] array.  bounds: (lo, hi),
+        float64 extremes per continuous column (in column order) to scale with instead of this table's own
+        (:func:`table_bounds`, :func:`combine_bounds`): shards of one table scaled with the table's bounds give the
+        distances the whole table gives (eval/fed_privacy.py)."""
         super().__init__(meta, device, ops, max_rows, graph)
         ops = self.ops
         kind = [NN_CAT if cat else NN_CONT for cat in self.is_cat]
@@ -113,8 +116,15 @@ class DevicePrivacy(DeviceEvaluator):
         cont_cols = torch.tensor([j for j, k in enumerate(kind) if k == NN_CONT], dtype=torch.long, device=dev)
         # MinMax on real, as stat_sim scales: lo and 1 / (hi - lo) of the real columns (1 for a constant column)
         rc = table[:, cont_cols]
-        self.lo = rc.min(dim=0).values.contiguous() if n_cont else torch.zeros(0, **f64)
-        hi = rc.max(dim=0).values if n_cont else torch.zeros(0, **f64)
+        if bounds is not None:
+            lo, hi = (np.ascontiguousarray(np.asarray(b, dtype=np.float64)).reshape(-1) for b in bounds)
+            if lo.shape != (n_cont,) or hi.shape != (n_cont,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+                raise ValueError(f"{self.who}: bounds are two finite float64 [{n_cont}] rows (lo, hi), one entry per "
+                                 "continuous column")
+            self.lo, hi = torch.from_numpy(lo).to(dev), torch.from_numpy(hi).to(dev)
+        else:
+            self.lo = rc.min(dim=0).values.contiguous() if n_cont else torch.zeros(0, **f64)
+            hi = rc.max(dim=0).values if n_cont else torch.zeros(0, **f64)
         span = hi - self.lo
         self.scale = torch.where(span > 0, 1.0 / torch.where(span > 0, span, torch.ones_like(span)),
                                  torch.ones_like(span)).contiguous()
@@ -165,6 +175,26 @@ class DevicePrivacy(DeviceEvaluator):
     def guard(self, min_dcr: float = 0.0) -> "PrivacyGuard":
         """A :class:`PrivacyGuard` of radius ``min_dcr`` around this evaluator's real rows, sharing its packed table."""
         return PrivacyGuard._sharing(self, min_dcr)
+
+
+def table_bounds(coded: np.ndarray, meta: dict) -> Tuple[np.ndarray, np.ndarray]:
+    """(lo, hi) of a coded [m, n_cols] table: the float64 extremes of its continuous columns, in column order --
+    what :class:`DevicePrivacy` scales with, and all of a client's shard that the federated audit shares."""
+    cont = [j for j, c in enumerate(meta["columns"]) if c["type"] != CATEGORICAL]
+    part = np.asarray(coded, dtype=np.float64)[:, cont]
+    if part.shape[0] < 1:
+        raise ValueError("table_bounds: the table is empty")
+    return part.min(axis=0), part.max(axis=0)
+
+
+def combine_bounds(pairs) -> Tuple[np.ndarray, np.ndarray]:
+    """The bounds of the union of the tables the (lo, hi) pairs came from: elementwise min / max, exact."""
+    pairs = [p for p in pairs if p is not None]
+    if not pairs:
+        raise ValueError("combine_bounds: no bounds")
+    lo = np.min(np.stack([np.asarray(p[0], dtype=np.float64) for p in pairs]), axis=0)
+    hi = np.max(np.stack([np.asarray(p[1], dtype=np.float64) for p in pairs]), axis=0)
+    return lo, hi
 
 
 def squared_radius(min_dcr) -> float:

@@ -54,6 +54,7 @@ from ..models.samplers import CondTables
 from ..parallel.comm import Comm
 from ..utils.metrics import MetricsLog, PhaseTimer, cgroup_cpu_stat
 from ..utils.devsync import PendingHost, stream_sync
+from .audit import FedAudit, privacy_on
 from .stats import (aggregation_weights, continuous_client_distances, continuous_client_distances_device,
                     merge_categorical_metas, uniform_weights)
 
@@ -165,6 +166,16 @@ class FedConfig:
     # need it).  The scores go to the metrics log and {name}_result/similarity_online.csv
     eval_every: int = 0
     eval_real: Optional[str] = None
+    # federated privacy audit and guard (fed/audit.py): the records stay on their clients, per-generated-row scalars
+    # travel.  privacy_every N: DCR / NNDR of every N-th round's table against every client's shard -> the metrics log,
+    # FedRuntime.privacy_rows and {name}_result/privacy_online.csv.  min_dcr T: after the last round the federator
+    # writes {name}_result/{name}_guarded.csv, guard_rows rows (default: n_sample) none of which lies within T of any
+    # client's record, in at most guard_max_passes passes.  Both off: a round issues exactly what it issues without them
+    privacy_every: int = 0
+    min_dcr: Optional[float] = None
+    guard_rows: Optional[int] = None
+    guard_max_passes: int = 64
+    keep_audit_table: bool = False          # tests: keep the last audited table and its scores (FedAudit.kept)
 
 
 def eval_needs_real_table(cfg: FedConfig, n_clients: int, world_size: int) -> bool:
@@ -268,6 +279,10 @@ class FedRuntime:
         self._round_start: Dict[int, float] = {}    # epoch -> wall time its round began
         self._csv_done: Dict[int, float] = {}       # epoch -> wall time its CSV was on disk
         self._csv_times: Dict[int, tuple] = {}      # epoch -> (copy wait, format + write) seconds, writer side
+        from .audit import refuse_unsupported
+        refuse_unsupported(cfg, comm)
+        self._audit = None                          # fed/audit.py FedAudit when privacy_every / min_dcr is set
+        self.privacy_rows: List[dict] = []          # federator: one record per audited epoch
 
     # ================================================================= data
     def _local_frame(self) -> pd.DataFrame:
@@ -335,6 +350,8 @@ class FedRuntime:
         stream -- the one that produced the rows -- ahead of the table's pinned copy; the two averages follow into
         a pinned row behind an event, and nothing here waits for the device.  A table the gather delivered on the
         host is uploaded first."""
+        if self._audit is not None:
+            self._audit.keep(table, epoch)
         sim = getattr(self, "_sim", None)
         every = int(self.cfg.eval_every)
         if sim is None or table is None or every <= 0 or (epoch + 1) % every:
@@ -402,6 +419,7 @@ class FedRuntime:
             df = self._local_frame()
             if list(df.columns) != list(spec.selected_variables):
                 df = df[spec.selected_variables]
+            self._frame = df if privacy_on(cfg) else None      # (coded again with the global vocabularies below)
             self.table = TablePreprocessor(df, f"{self.name}_train", spec.problem_type,
                                            "" if spec.target_column == "none" else spec.target_column,
                                            spec.categorical_list, spec.nonnegative_list, spec.date_dic)
@@ -506,6 +524,10 @@ class FedRuntime:
             self._prepare_batched()
         self.csv_cols = csv_layout(merged, self.vocabs)     # None: a date format only the pandas path handles
         self._prepare_similarity()      # (its uploads come before the barrier below, like every other one)
+        if privacy_on(cfg):
+            self._audit = FedAudit(self)
+            self.privacy_rows = self._audit.rows
+            self._frame = None
         if getattr(self, "thread_local_capture", False):
             # client threads of one process: none captures its graphs while another still uploads its tables (a
             # pageable host-to-device copy fails while any stream of the process captures -- with independent
@@ -612,7 +634,7 @@ class FedRuntime:
         local_rows = self.rows[first:first + g.k]
         ok = (self.device.type == "cuda" and cfg.backend in ("auto", "hip") and cfg.drop_client_prob <= 0 and
               c.client_ranks == list(range(c.world_size)) and g.k > 1 and cfg.mode == "fedavg")
-        if ok and cfg.batched_clients == "auto" and g.k > cfg.batched_max_auto:
+        if ok and cfg.batched_clients == "auto" and (g.k > cfg.batched_max_auto or privacy_on(cfg)):
             return None
         if not ok:
             if cfg.batched_clients == "on":
@@ -977,10 +999,11 @@ class FedRuntime:
         self._csv_times[epoch] = (t1 - t0, time.perf_counter() - t1)
         return path
 
-    def _write_epoch_csv_body(self, values, epoch: int):
+    def _write_epoch_csv_body(self, values, epoch: int, path: Optional[str] = None):
         if isinstance(values, PendingHost):
             values = values.get()
-        path = os.path.join(self.result_dir(), f"{self.name}_synthesis_epoch_{epoch}.csv")
+        if path is None:
+            path = os.path.join(self.result_dir(), f"{self.name}_synthesis_epoch_{epoch}.csv")
         use_native = self.cfg.csv_writer in ("auto", "native") and self.csv_cols is not None
         if use_native:
             from ..utils import csvio
@@ -1046,6 +1069,8 @@ class FedRuntime:
             with self.timer.phase("sample_dump", self.device):
                 self.sample_round(epoch, aggregated)
         h3 = time.perf_counter()
+        if self._audit is not None:
+            self._audit.note_round(epoch, dump)
         if self.device.type == "cuda" and self.cfg.round_sync:
             stream_sync(self.device)
         dt = time.time() - t0
@@ -1129,6 +1154,10 @@ class FedRuntime:
                 self.flush_writes()      # the checkpoint's per-round stamps include every CSV so far
                 self.save_checkpoint(ep + 1)
         self.flush_writes()
+        if self._audit is not None:         # (collective: a deferred hand-off's table, then the guarded table)
+            self._audit.drain()
+            self._audit.write_online()
+            self._audit.guarded_table()
         if self.gradflow is not None:
             d = os.path.join(cfg.out_dir, "reports")
             os.makedirs(d, exist_ok=True)

@@ -678,6 +678,16 @@ class HipOps:
         """Same contract as TorchOps.guard_mark."""
         self.L.guard_mark(near, tgt, stats)
 
+    NN_MAX_SHARDS = 64      # kernels/launch.h: shards one merge folds
+
+    def nn_merge_shards(self, parts, offsets, d1, d2, i1, owner, by_client):
+        """Same contract as TorchOps.nn_merge_shards (kernels/privacy.hip nn_merge_shards_kernel)."""
+        self.L.nn_merge_shards(parts, offsets, d1, d2, i1, owner, by_client)
+
+    def nn_within_merge_shards(self, near, offsets, near_out, owner):
+        """Same contract as TorchOps.nn_within_merge_shards."""
+        self.L.nn_within_merge_shards(near, offsets, near_out, owner)
+
     def nn_stats(self, d1, d2, n, keys, tmp, part, out):
         """Same contract as TorchOps.nn_stats; tmp: scratch of keys' shape (the sort's), part: float64
         [>= nn_stats_part(n)]."""

@@ -695,6 +695,61 @@ class TorchOps:
         stats[0] += m
         stats[1] += int(rej.sum())
 
+    NN_MAX_SHARDS = 64                                           # kernels/launch.h: shards one merge folds
+
+    def nn_merge_shards(self, parts, offsets, d1, d2, i1, owner, by_client):
+        """The nearest-neighbour answers of K shards folded into the answer over their union (eval/fed_privacy.py).
+
+        parts float64 [K, n, 3]: shard k's nn_top2 result per query row as (d1, d2, i1 as a float64; -1: no
+        candidate); offsets int64 [K]: the exclusive prefix sums of the shard row counts.  The shards are folded in
+        order with strict <, a shard's d2 competing with the others' d1, so d1 <= d2 are the two smallest distances
+        over the union with multiplicity and i1 (int32) = offsets[k] + local is the lowest global index at distance
+        d1; owner (int32) = that k, or -1 where no shard has a candidate (d1 = +inf, i1 = -1).  by_client int64
+        [2, K] is overwritten: row 0 = query rows whose nearest record shard k holds, row 1 = query rows of which
+        shard k holds an exact copy (its d1 == 0)."""
+        K, n = int(parts.shape[0]), int(parts.shape[1])
+        if K < 1 or K > self.NN_MAX_SHARDS:
+            raise ValueError(f"nn_merge_shards: 1..{self.NN_MAX_SHARDS} shards, got {K}")
+        dev = parts.device
+        inf = float("inf")
+        a1 = torch.full((n,), inf, dtype=torch.float64, device=dev)
+        a2 = torch.full((n,), inf, dtype=torch.float64, device=dev)
+        ai = torch.full((n,), -1, dtype=torch.int64, device=dev)
+        ao = torch.full((n,), -1, dtype=torch.int64, device=dev)
+        by_client.zero_()
+        for k in range(K):
+            b1, b2 = parts[k, :, 0], parts[k, :, 1]
+            local = parts[k, :, 2].to(torch.int64)
+            win = (b1 < a1) & (local >= 0)
+            second = ~win & (b1 < a2)
+            a2 = torch.where(win, torch.where(b2 < a1, b2, a1), torch.where(second, b1, a2))
+            a1 = torch.where(win, b1, a1)
+            ai = torch.where(win, offsets[k] + local, ai)
+            ao = torch.where(win, torch.full_like(ao, k), ao)
+            by_client[1, k] = (b1 == 0).sum()
+        for k in range(K):
+            by_client[0, k] = (ao == k).sum()
+        d1[:n] = a1
+        d2[:n] = a2
+        i1[:n] = ai.to(i1.dtype)
+        owner[:n] = ao.to(owner.dtype)
+
+    def nn_within_merge_shards(self, near, offsets, near_out, owner):
+        """The radius answers of K shards folded: near int32 [K, n] (shard k's lowest local hit or -1), offsets int64
+        [K] -> near_out int32 [n] = offsets[k] + near[k] of the first shard with a hit (the lowest global index), or
+        -1; owner int32 [n] = that k or -1."""
+        K, n = int(near.shape[0]), int(near.shape[1])
+        if K < 1 or K > self.NN_MAX_SHARDS:
+            raise ValueError(f"nn_within_merge_shards: 1..{self.NN_MAX_SHARDS} shards, got {K}")
+        hit = torch.full((n,), -1, dtype=torch.int64, device=near.device)
+        own = torch.full((n,), -1, dtype=torch.int64, device=near.device)
+        for k in range(K):
+            take = (own < 0) & (near[k] >= 0)
+            hit = torch.where(take, offsets[k] + near[k].to(torch.int64), hit)
+            own = torch.where(take, torch.full_like(own, k), own)
+        near_out[:n] = hit.to(near_out.dtype)
+        owner[:n] = own.to(owner.dtype)
+
     def nn_stats(self, d1, d2, n, keys, tmp, part, out):
         """Table scores of rows [0, n): keys [2, >= n] receives DCR = sqrt(d1) and NNDR = sqrt(d1 / d2) (1 where
         d2 == 0, 0 where d2 = +inf), each row ascending; out[0], out[1] = their 5th percentiles with numpy's linear
