@@ -1197,6 +1197,88 @@ void pred_mark(const Tensor& pred_j, const Tensor& pred_kind, const Tensor& pred
   fedtgan::launch_pred_mark(a, cur_stream());
 }
 
+// completion of partial rows (kernels/known_gen.hip)
+void known_request(const Tensor& qidx, const Tensor& drv_span, const Tensor& drv_opt, int64_t tries, const Tensor& col,
+                   const Tensor& opt, const optional<Tensor>& h, int64_t cc, const Tensor& cond_off,
+                   const Tensor& cond_w) {
+  auto i32 = [](const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(); };
+  TORCH_CHECK(tries >= 1 && tries <= fedtgan::KNOWN_MAX_TRIES, "known_request: 1..", fedtgan::KNOWN_MAX_TRIES,
+              " tries, got ", tries);
+  TORCH_CHECK(i32(qidx) && i32(drv_span) && i32(drv_opt) && drv_opt.numel() == drv_span.numel(),
+              "known_request: int32 qidx [slots] and drv_span / drv_opt [queries]");
+  const int64_t rows = qidx.numel() * tries;
+  TORCH_CHECK(rows < (int64_t)INT32_MAX, "known_request: a pass holds fewer than 2^31 rows");
+  TORCH_CHECK(i32(col) && i32(opt) && col.numel() >= rows && opt.numel() >= rows,
+              "known_request: col / opt must be int32 with one entry per row");
+  TORCH_CHECK(i32(cond_off) && i32(cond_w) && cond_w.numel() == cond_off.numel() && cond_off.numel() >= 1,
+              "known_request: int32 span tables");
+  fedtgan::KnownRequestArgs a{};
+  a.qidx = qidx.data_ptr<int>();
+  a.n_slots = (int)qidx.numel();
+  a.tries = (int)tries;
+  a.n_query = drv_span.numel();
+  a.drv_span = drv_span.data_ptr<int>();
+  a.drv_opt = drv_opt.data_ptr<int>();
+  a.col = col.data_ptr<int>();
+  a.opt = opt.data_ptr<int>();
+  a.cond_off = cond_off.data_ptr<int>();
+  a.cond_w = cond_w.data_ptr<int>();
+  a.n_span = (int)cond_off.numel();
+  if (h.has_value() && h->defined()) {
+    check_f32_2d(*h, "known_request h");
+    TORCH_CHECK(h->size(0) >= rows && cc >= 0 && cc < h->size(1), "known_request: h rows / conditional block");
+    a.h = fp(*h);
+    a.ldh = ld_of(*h);
+    a.cc = (int)cc;
+    a.C = (int)(h->size(1) - cc);
+  }
+  fedtgan::launch_known_request(a, cur_stream());
+}
+
+void known_match(const Tensor& known, const Tensor& mask, const Tensor& qidx, int64_t tries, const Tensor& cand,
+                 const Tensor& kind, const Tensor& scale, const Tensor& best, const Tensor& dc, const Tensor& miss,
+                 const Tensor& seen, const Tensor& pick, const Tensor& dst) {
+  auto dev = [](const Tensor& t, at::ScalarType ty) { return t.is_cuda() && t.scalar_type() == ty && t.is_contiguous(); };
+  TORCH_CHECK(tries >= 1 && tries <= fedtgan::KNOWN_MAX_TRIES, "known_match: 1..", fedtgan::KNOWN_MAX_TRIES,
+              " tries, got ", tries);
+  TORCH_CHECK(dev(known, at::kDouble) && known.dim() == 2 && dev(mask, at::kByte) && mask.dim() == 2 &&
+                  mask.size(0) == known.size(0) && mask.size(1) == known.size(1),
+              "known_match: known float64 [queries, n_cols] and mask uint8 of the same shape");
+  const int64_t nq = known.size(0), n_cols = known.size(1);
+  TORCH_CHECK(n_cols >= 1 && n_cols <= 1024, "known_match: 1..1024 columns, got ", n_cols);
+  TORCH_CHECK(nq < (int64_t)INT32_MAX, "known_match: fewer than 2^31 queries");
+  TORCH_CHECK(dev(qidx, at::kInt), "known_match: qidx int32 [slots]");
+  TORCH_CHECK(dev(cand, at::kDouble) && cand.dim() == 2 && cand.size(1) == n_cols &&
+                  cand.size(0) >= qidx.numel() * tries && cand.numel() < (int64_t)INT32_MAX,
+              "known_match: cand float64 [>= slots * tries, n_cols], fewer than 2^31 values");
+  TORCH_CHECK(dev(kind, at::kInt) && kind.numel() == n_cols && dev(scale, at::kDouble) && scale.numel() == n_cols,
+              "known_match: int32 kind and float64 scale, one entry per column");
+  TORCH_CHECK(dev(best, at::kDouble) && dev(dc, at::kDouble) && dev(miss, at::kInt) && dev(seen, at::kLong) &&
+                  dev(pick, at::kLong) && best.numel() >= nq && dc.numel() >= nq && miss.numel() >= nq &&
+                  seen.numel() >= nq && pick.numel() >= nq,
+              "known_match: best / dc float64, miss int32, seen / pick int64, one entry per query");
+  TORCH_CHECK(dev(dst, at::kDouble) && dst.dim() == 2 && dst.size(0) >= nq && dst.size(1) == n_cols,
+              "known_match: dst float64 [queries, n_cols]");
+  fedtgan::KnownMatchArgs a{};
+  a.known = known.data_ptr<double>();
+  a.mask = mask.data_ptr<uint8_t>();
+  a.n_query = nq;
+  a.n_cols = (int)n_cols;
+  a.qidx = qidx.data_ptr<int>();
+  a.n_slots = (int)qidx.numel();
+  a.tries = (int)tries;
+  a.cand = cand.data_ptr<double>();
+  a.kind = kind.data_ptr<int>();
+  a.scale = scale.data_ptr<double>();
+  a.best = best.data_ptr<double>();
+  a.dc = dc.data_ptr<double>();
+  a.miss = miss.data_ptr<int>();
+  a.seen = seen.data_ptr<int64_t>();
+  a.pick = pick.data_ptr<int64_t>();
+  a.dst = dst.data_ptr<double>();
+  fedtgan::launch_known_match(a, cur_stream());
+}
+
 // ----------------------------------------------------------------------------- similarity evaluator
 namespace {
 bool sim_i32(const Tensor& t) { return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(); }
@@ -2248,6 +2330,7 @@ int64_t check_status() {
   (void)hipDeviceSynchronize();
   return (int64_t)(fedtgan::check_status_gemm() | fedtgan::check_status_ctgan_ops() | fedtgan::check_status_vgm() |
                    fedtgan::check_status_cond_gen() | fedtgan::check_status_cond_pred() |
+                   fedtgan::check_status_known_gen() |
                    fedtgan::check_status_similarity() |
                    fedtgan::check_status_forest());
 }
@@ -2510,6 +2593,12 @@ TORCH_LIBRARY(fedtgan, m) {
       "pred_mark(Tensor pred_j, Tensor pred_kind, Tensor pred_lo, Tensor pred_hi, Tensor pred_lut_off, "
       "Tensor pred_lut_len, Tensor pred_lut, Tensor(a!) pred_stats, Tensor out, Tensor(b!) tgt) -> ()");
   m.def(
+      "known_request(Tensor qidx, Tensor drv_span, Tensor drv_opt, int tries, Tensor(a!) col, Tensor(b!) opt, "
+      "Tensor(c!)? h, int cc, Tensor cond_off, Tensor cond_w) -> ()");
+  m.def(
+      "known_match(Tensor known, Tensor mask, Tensor qidx, int tries, Tensor cand, Tensor kind, Tensor scale, "
+      "Tensor(a!) best, Tensor(b!) dc, Tensor(c!) miss, Tensor(d!) seen, Tensor(e!) pick, Tensor(f!) dst) -> ()");
+  m.def(
       "sim_prepare(Tensor values, Tensor kind, Tensor slot, Tensor vocab, Tensor(a!) keys, Tensor(b!) valid, "
       "Tensor(c!) counts) -> ()");
   m.def("sim_sort(Tensor(a!) keys, Tensor(b!) tmp, int n) -> ()");
@@ -2660,6 +2749,8 @@ TORCH_LIBRARY_IMPL(fedtgan, CUDA, m) {
   m.impl("adam_cs", &adam_cs);
   m.impl("sample_decode", &sample_decode);
   m.impl("rng_bump", &rng_bump);
+  m.impl("known_request", &known_request);
+  m.impl("known_match", &known_match);
   m.impl("cond_request", &cond_request);
   m.impl("cond_partition", &cond_partition);
   m.impl("pred_request", &pred_request);

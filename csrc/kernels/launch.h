@@ -505,6 +505,46 @@ struct PredMarkArgs {
 void launch_pred_mark(const PredMarkArgs& a, hipStream_t stream);
 unsigned check_status_cond_pred();
 
+// Completion of partial rows (kernels/known_gen.hip): every known row (query) has its own condition, its own block
+// of `tries` consecutive candidate rows of a pass (a slot) and its own best candidate so far.  The table, its
+// per-row drivers and the per-query state live in device buffers; a pass names its queries in qidx, so one captured
+// pass serves every pass of the same size.
+constexpr int KNOWN_MAX_TRIES = 1024;   // candidate rows per query and pass
+struct KnownRequestArgs {
+  const int* qidx;           // [n_slots] the slot's query, -1: idle
+  int n_slots, tries;        // rows of the pass = n_slots * tries
+  int64_t n_query;           // rows of drv_span / drv_opt
+  const int* drv_span;       // [n_query] cond-span that drives the query's rows, -1: none (the sampler's draw stays)
+  const int* drv_opt;        // [n_query] ... and its option
+  int* col;                  // [rows] as CondRequestArgs
+  int* opt;
+  float* h;
+  int ldh, cc, C;
+  const int* cond_off;
+  const int* cond_w;
+  int n_span;
+};
+void launch_known_request(const KnownRequestArgs& a, hipStream_t stream);
+struct KnownMatchArgs {
+  const double* known;       // [n_query, n_cols] the partial table (an unknown cell's value is never read)
+  const uint8_t* mask;       // [n_query, n_cols] != 0: the cell is known
+  int64_t n_query;
+  int n_cols;
+  const int* qidx;           // [n_slots]
+  int n_slots, tries;
+  const double* cand;        // [n_slots * tries, n_cols] decoded pass; slot s owns rows s * tries ...
+  const int* kind;           // [n_cols] 0: continuous, 1: categorical (codes compared, never used as an index)
+  const double* scale;       // [n_cols] continuous columns: 1 / (max - min)
+  double* best;              // [n_query] smallest d2 so far (+inf before the first pass)
+  double* dc;                // [n_query] its continuous part
+  int* miss;                 // [n_query] its categorical mismatches
+  int64_t* seen;             // [n_query] candidates judged so far
+  int64_t* pick;             // [n_query] the best candidate's number among them
+  double* dst;               // [n_query, n_cols] completed rows
+};
+void launch_known_match(const KnownMatchArgs& a, hipStream_t stream);
+unsigned check_status_known_gen();
+
 // Similarity evaluator (kernels/similarity.hip): Avg_JSD / Avg_WD of a decoded table against a real one, on the
 // device.  Counting is in integers and every fp64 sum has a fixed order, so a table scores bit-identically on every
 // run; no launch allocates or waits on the host.

@@ -37,6 +37,15 @@ def main(argv=None):
                         "-privacy_against (0 keeps out exact copies); still exactly -n rows")
     p.add_argument("-guard_against", default=None, metavar="REAL.csv",
                    help="the real table of -min_dcr (default: the table of -privacy_against)")
+    p.add_argument("-known", default=None, metavar="PARTIAL.csv",
+                   help="complete a partial table: a CSV with (some of) the model's columns whose blank cells are to be "
+                        "filled; the output has its rows, in its order, with the known cells kept and the others taken "
+                        "from the closest of -known_tries generated candidates (-n is ignored)")
+    p.add_argument("-known_tries", type=int, default=64, help="candidates generated per row of -known (1..1024)")
+    p.add_argument("-known_retries", type=int, default=2,
+                   help="further rounds of candidates for rows of -known that still miss a known category")
+    p.add_argument("-known_tol", type=float, default=None, metavar="T",
+                   help="also retry rows of -known whose known numeric cells lie farther than T from the candidate")
     p.add_argument("-score_against", default=None, metavar="REAL.csv",
                    help="also print Avg_JSD / Avg_WD of the generated rows against this table, scored on the device")
     p.add_argument("-privacy_against", default=None, metavar="REAL.csv",
@@ -89,6 +98,23 @@ def main(argv=None):
         p.error("-min_dcr is a finite number >= 0")
     if args.guard_against and args.min_dcr is None:
         p.error("-guard_against needs -min_dcr")
+    if args.known is not None:
+        clash = [f for f, v in (("-where", args.where), ("-where_json", args.where_json),
+                                ("-where_range", args.where_range), ("-min_dcr", args.min_dcr is not None),
+                                ("-guard_against", args.guard_against), ("-score_against", args.score_against),
+                                ("-privacy_against", args.privacy_against), ("-corr_against", args.corr_against),
+                                ("-fidelity_against", args.fidelity_against),
+                                ("-utility_against", args.utility_against)) if v]
+        if clash:
+            p.error(f"-known does not combine with {', '.join(clash)}")
+        if not 1 <= args.known_tries <= 1024:
+            p.error("-known_tries is 1..1024")
+        if args.known_retries < 0:
+            p.error("-known_retries is >= 0")
+        if args.known_tol is not None and not args.known_tol >= 0:
+            p.error("-known_tol is a number >= 0")
+    elif args.known_tries != 64 or args.known_retries != 2 or args.known_tol is not None:
+        p.error("-known_tries / -known_retries / -known_tol need -known")
     import torch
     from fed_tgan_amd.models.conditional import parse_where
     from fed_tgan_amd.models.generator_io import load_generator
@@ -101,6 +127,18 @@ def main(argv=None):
     out = args.out or f"{gen.name}_synthetic.csv"
     t0 = time.time()
     scores = privacy = corr = utility = fidelity = None
+    if args.known is not None:
+        try:
+            gen.write_csv(out, known=args.known, tries=args.known_tries, retries=args.known_retries,
+                          tol=args.known_tol)
+        except ValueError as e:
+            p.error(str(e))
+        lk = gen.engine.last_known
+        print(f"{lk['rows']} rows -> {out} ({time.time() - t0:.3f} s, {gen.engine.ops.name} on {dev}, completed from "
+              f"{args.known}: {lk['sweeps']} sweeps, {lk['generated']} candidates generated, "
+              f"{100.0 * lk['exact_categorical']:.1f} % of rows with every known category matched, "
+              f"d_p95 {lk['d_p95']:.4g})", flush=True)
+        return out
     if args.score_against or args.privacy_against or args.corr_against or args.utility_against or \
             args.fidelity_against:
         scores, privacy, corr, utility, *more = gen.write_csv_all(

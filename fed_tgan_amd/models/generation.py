@@ -35,12 +35,14 @@ class GenerationMixin:
         self.gen_tables = self.gen_cond = self.gen_counts = None    # set_generation_tables
         # _gen_bufs: (H, logits, col, opt) of the eager passes, grown on demand; _gen_graphs / _gen_split: n -> the
         # captured generate_decoded(n) / prep + body of generate_decoded_split(n); _cond_ent: (m, bins, fixed
-        # columns) -> buffers / hipGraph of a conditional pass, _guard_ent: the same of a guarded pass; _gen_prepped:
-        # event, the last pipelined prep is issued
+        # columns) -> buffers / hipGraph of a conditional pass, _guard_ent: the same of a guarded pass; _known_ent:
+        # (m, tries) -> the same of a completion pass; _gen_prepped: event, the last pipelined prep is issued
         self._drop_generation()
         self._gen_done = None                     # event: the last pipelined generation body has finished
         self.last_conditional = None              # generate_decoded_where: passes, rows generated / kept, filled counts
         self.last_guard = None                    # generate_decoded_guarded: passes, rows generated / rejected / kept
+        self.last_known = None                    # generate_decoded_known: sweeps, rows generated / open, distances
+        self._known_transformer = None            # set_generation_tables: the transformer build_known reads
         self._gw16 = self._gwt = None             # bf16 / transposed generation copies of the generator weights
         self._gsnap = self._gsnap_pairs = self._gsnap_ctr = None      # pipelined generation: parameter / RNG snapshot
 
@@ -68,6 +70,7 @@ class GenerationMixin:
         self.gen_counts = np.asarray(cond.counts, dtype=np.float64)      # the span counts a driving range / set weighs
         self.gen_tables = {"cols": cols, "mu": torch.as_tensor(mu, dtype=torch.float64, device=dev),
                            "sd": torch.as_tensor(sd, dtype=torch.float64, device=dev)}
+        self._known_transformer = transformer
         self._drop_generation()
 
     def _drop_generation(self) -> None:
@@ -77,6 +80,7 @@ class GenerationMixin:
         self._gen_split: Dict[int, GenGraph] = {}
         self._cond_ent: Dict[tuple, dict] = {}
         self._guard_ent: Dict[tuple, dict] = {}
+        self._known_ent: Dict[tuple, dict] = {}
         self._gen_bufs = self._gen_prepped = None
 
     def _prepare_generation_graphs(self, gen_rows: Sequence[int], gen_split: bool) -> None:
@@ -613,6 +617,147 @@ class GenerationMixin:
                 req["pred_stats"].zero_()
         run = partial(self._guard_pass, ent, m)
         ent["graph"], = warm_and_capture(self.device, run, [run], snapshot=ctr.clone, restore=restore,
+                                         mode=self.capture_mode)
+
+    # ------------------------------------------------------------------ completion of partial rows
+    @torch.no_grad()
+    def generate_decoded_known(self, known, mask, tries: int = 64, retries: int = 2, tol: float | None = None,
+                               chunk: int | None = None, use_graph: bool | None = None) -> torch.Tensor:
+        """The unknown cells of a known table: [N, n_cols] float64 on the device, row i carrying the known cells of
+        input row i (their bits) and, in the others, the cells of the closest of the candidates generated for it.
+
+        ``known`` [N, n_cols] float64 in the decoded space and ``mask`` [N, n_cols] (non-zero: the cell is known);
+        models/known.py parse_known makes them from a frame or a CSV, build_known the per-row drivers.  One pass over
+        m = q * tries rows (``chunk``: the rows of a pass, rounded down to a multiple of ``tries``) serves q rows of
+        the table: sample_gen -> known_request (the rows of a slot take their query's condition) -> eval generator
+        -> sample_decode -> known_match (each query keeps the lowest candidate with the smallest distance to its
+        known cells, if strictly closer than its best so far).  Sweep 0 serves every row; up to ``retries`` further
+        sweeps serve the rows that are still open -- a known category missed, or sqrt(dc) above ``tol`` (default:
+        no bound, only categorical mismatches reopen) -- listed on the device in ascending order, with one readback
+        (their count) per sweep.  Rows that stay open raise nothing: ``self.last_known`` says how many.
+
+        On the HIP backend with cfg.gen_graph the pass is captured once per (m, tries) and replayed, the pass's
+        queries copied into the static buffer before each replay; the RNG counter is restored after the warm-up, so
+        eager and replayed runs from equal engine states give bit-identical tables and statistics.
+        ``self.last_known``: rows, tries, sweeps, generated, open (after each sweep), exact_categorical (share of
+        rows with no known category missed) and d_p50 / d_p95 / d_max of sqrt(dc)."""
+        from .known import build_known
+        if self.gen_tables is None:
+            raise RuntimeError("set_generation_tables() first")
+        R = int(tries)
+        if not 1 <= R <= int(self.ops.KNOWN_MAX_TRIES):
+            raise ValueError(f"tries must be 1..{self.ops.KNOWN_MAX_TRIES}, got {tries}")
+        if int(retries) < 0:
+            raise ValueError("retries must be non-negative")
+        tol2 = float("inf") if tol is None else float(tol) * float(tol)
+        if not tol2 >= 0:
+            raise ValueError(f"tol must be a number >= 0, got {tol!r}")
+        to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)      # noqa: E731
+        tab = build_known(self._known_transformer, self.gen_counts, to_np(known), to_np(mask))
+        N = int(tab["known"].shape[0])
+        if N == 0:
+            self.last_known = {"rows": 0, "tries": R, "sweeps": 0, "generated": 0, "open": [],
+                               "exact_categorical": 1.0, "d_p50": 0.0, "d_p95": 0.0, "d_max": 0.0}
+            return self._decoded(0)
+        if use_graph is None:
+            use_graph = self._graphs_for_generation()
+        if chunk is not None:
+            if int(chunk) < 1:
+                raise ValueError("chunk must be positive")
+            q = max(1, int(chunk) // R)
+        else:       # passes as large as the plain generation's, or one pass when the table needs fewer rows
+            q = max(1, min(int(self.cfg.gen_chunk) // R, 1 << int(np.ceil(np.log2(N)))))
+        m = q * R
+        self._wait_gen_done()
+        ent = self._known_entry(m, R, N)
+        dev = self.device
+        for k in ("known", "mask", "drv_span", "drv_opt"):
+            ent[k][:N].copy_(torch.from_numpy(tab[k]).to(dev))
+        ent["kind"].copy_(torch.from_numpy(tab["kind"]).to(dev))
+        ent["scale"].copy_(torch.from_numpy(tab["scale"]).to(dev))
+        st = ent["state"]
+        st["best"].fill_(float("inf"))
+        for k in ("dc", "miss", "seen", "pick"):
+            st[k].zero_()
+        ent["dst"].zero_()
+        if use_graph and ent.get("graph") is None:
+            self._capture_known(ent, m, R)
+        todo = torch.arange(N, dtype=torch.int32, device=dev)
+        opened, passes, sweeps = [], 0, 0
+        while True:
+            n_open = int(todo.numel())
+            # the sweep's queries, padded with idle slots to whole passes: one copy per pass
+            pad = torch.full((-(-n_open // q) * q,), -1, dtype=torch.int32, device=dev)
+            pad[:n_open] = todo
+            for a in range(0, int(pad.numel()), q):
+                ent["qidx"].copy_(pad[a:a + q])
+                if use_graph:
+                    ent["graph"].replay()
+                else:
+                    self._known_pass(ent, m, R)
+                passes += 1
+            sweeps += 1
+            todo = torch.nonzero((st["miss"][:N] > 0) | (st["dc"][:N] > tol2)).view(-1).to(torch.int32)
+            opened.append(int(todo.numel()))          # the one readback per sweep
+            if opened[-1] == 0 or sweeps > int(retries):
+                break
+        out = ent["dst"][:N].clone()
+        d = torch.sqrt(st["dc"][:N]).cpu().numpy()
+        self.last_known = {"rows": N, "tries": R, "sweeps": sweeps, "generated": passes * m, "open": opened,
+                           "exact_categorical": float((st["miss"][:N] == 0).double().mean()),
+                           "d_p50": float(np.percentile(d, 50)), "d_p95": float(np.percentile(d, 95)),
+                           "d_max": float(d.max())}
+        if hasattr(self.ops, "check"):
+            self.ops.check()
+        return out
+
+    def _known_entry(self, m: int, R: int, N: int) -> dict:
+        """Static buffers of a completion pass over m rows of ``R`` tries: the pass's activations / logits /
+        conditions / decoded rows and its queries, and -- sized for the largest table seen (grown, and the graph
+        dropped, when a table has more rows) -- the table, its drivers, the per-query state and the completed rows."""
+        key = (m, R)
+        ent = self._known_ent.get(key)
+        dev = self.device
+        n_cols = len(self.gen_tables["cols"])
+        if ent is None:
+            H, lg, col, opt = self._gen_alloc(m, self.gen16)
+            ent = {"H": H, "lg": lg, "col": col, "opt": opt, "out": self._decoded(m),
+                   "qidx": torch.full((m // R,), -1, dtype=torch.int32, device=dev),
+                   "kind": torch.zeros(n_cols, dtype=torch.int32, device=dev),
+                   "scale": torch.ones(n_cols, dtype=torch.float64, device=dev), "cap": 0, "graph": None}
+            self._known_ent[key] = ent
+        if ent["cap"] < N:
+            if ent["graph"] is not None:
+                torch.cuda.synchronize(dev)
+            ent["graph"] = None
+            z = lambda dt, *shape: torch.zeros(*shape, dtype=dt, device=dev)      # noqa: E731
+            ent.update({"known": z(torch.float64, N, n_cols), "mask": z(torch.uint8, N, n_cols),
+                        "drv_span": torch.full((N,), -1, dtype=torch.int32, device=dev),
+                        "drv_opt": z(torch.int32, N), "dst": self._decoded(N),
+                        "state": {"best": z(torch.float64, N), "dc": z(torch.float64, N), "miss": z(torch.int32, N),
+                                  "seen": z(torch.int64, N), "pick": z(torch.int64, N)},
+                        "cap": N})
+        return ent
+
+    def _known_pass(self, ent: dict, m: int, R: int):
+        o = self.ops
+        H, lg, col, opt = ent["H"], ent["lg"], ent["col"], ent["opt"]
+        w16 = self._gen_weights16() if self.gen16 else None
+        o.sample_gen(self.gen_cond, H, self.c_cols, self.z_cols, col_out=col, opt_out=opt, stream_id=21)
+        o.known_request(ent["qidx"], ent["drv_span"], ent["drv_opt"], R, col, opt, self.gen_cond,
+                        h=None if w16 is not None else H, c_col0=self.c_cols[0])
+        self._gen_forward(H, lg, col, opt, w16)
+        o.sample_decode(lg, ent["out"], self.gen_tables, stream_id=23)
+        o.known_match(ent["known"], ent["mask"], ent["qidx"], R, ent["out"], ent["kind"], ent["scale"], ent["state"],
+                      ent["dst"])
+
+    def _capture_known(self, ent: dict, m: int, R: int):
+        """Capture one completion pass.  The warm-up runs with every slot idle, so it writes no query's state; the RNG
+        counter is put back after it (see _capture_cond)."""
+        ctr = self.ops.ctr
+        ent["qidx"].fill_(-1)
+        run = partial(self._known_pass, ent, m, R)
+        ent["graph"], = warm_and_capture(self.device, run, [run], snapshot=ctr.clone, restore=ctr.copy_,
                                          mode=self.capture_mode)
 
     # ------------------------------------------------------------------ pipelined generation

@@ -89,13 +89,60 @@ class LoadedGenerator:
         torch.cuda.current_stream(vals.device).synchronize()
         return host.numpy()
 
-    def write_csv(self, path: str, n: int, threads: int = 0, where=None, max_passes: int = 64, min_dcr=None,
-                  guard_real=None) -> str:
+    def write_csv(self, path: str, n: Optional[int] = None, threads: int = 0, where=None, max_passes: int = 64,
+                  min_dcr=None, guard_real=None, known=None, tries: int = 64, retries: int = 2, tol=None) -> str:
+        """``n`` generated rows as a CSV; with ``known`` (a partial table, :meth:`complete`) its completed rows
+        instead, in its row order (``n``, ``where`` and the guard do not combine with it)."""
+        if known is not None:
+            if where or min_dcr is not None or guard_real is not None:
+                raise ValueError("known does not combine with where, min_dcr or guard_real")
+            return self._write_values(path, self.complete(known, tries=tries, retries=retries, tol=tol), threads)
+        if n is None:
+            raise ValueError("write_csv needs the number of rows n (or a partial table: known=)")
         if min_dcr is not None:
             vals = self.sample(n, where=where or None, max_passes=max_passes, min_dcr=min_dcr, guard_real=guard_real)
         else:
             vals = self.sample(n, where=where, max_passes=max_passes) if where else self.sample(n)
         return self._write_values(path, vals, threads)
+
+    def _known_arrays(self, known):
+        """(known, mask) of a partial table: a DataFrame or a CSV path (models/known.py parse_known), or the pair
+        of arrays itself."""
+        if isinstance(known, tuple) and len(known) == 2:
+            return known
+        from .known import parse_known
+        return parse_known(known, self.meta, self.vocabs, self.transformer)
+
+    def complete(self, known, tries: int = 64, retries: int = 2, tol=None) -> np.ndarray:
+        """The unknown cells of a partial table filled in: [N, n_columns] decoded values, float64, one row per input
+        row in the input's order.  ``known``: a DataFrame or a CSV path whose blank cells are the holes (columns by
+        name; models/known.py parse_known), or a pair (known float64 [N, n_columns] in the decoded space, mask).
+        Every row's known cells come back as given; its other cells are those of the closest of ``tries`` rows
+        generated under the row's own condition, so the row is an approximation of "a row of the model with these
+        cells", and how close it got is in ``engine.last_known`` (``exact_categorical``, ``d_p50`` / ``d_p95`` /
+        ``d_max``).  Rows that miss a known category (or, with ``tol``, lie farther than it) get up to ``retries``
+        further rounds of candidates."""
+        k, m = self._known_arrays(known)
+        return self._to_host(self.engine.generate_decoded_known(k, m, tries=tries, retries=retries, tol=tol))
+
+    def complete_frame(self, known, tries: int = 64, retries: int = 2, tol=None):
+        """:meth:`complete` as a DataFrame in the CSV's value space (labels, expm1 of the non-negative columns), with
+        the caller's own known cells spliced back verbatim."""
+        import pandas as pd
+        k, m = self._known_arrays(known)
+        vals = self._to_host(self.engine.generate_decoded_known(k, m, tries=tries, retries=retries, tol=tol))
+        out = decode_frame(vals, self.meta, self.vocabs)
+        if isinstance(known, tuple):
+            return out
+        src = known if isinstance(known, pd.DataFrame) else pd.read_csv(known, dtype=str, keep_default_na=False)
+        names = [c["column_name"] for c in self.meta["columns"]]
+        for j, name in enumerate(names):
+            if name in src.columns and name in out.columns and bool(np.asarray(m)[:, j].any()):
+                on = np.asarray(m)[:, j] != 0
+                col = out[name].astype(object)
+                col[on] = src[name].to_numpy(dtype=object)[on]
+                out[name] = col
+        return out
 
     def _write_values(self, path: str, vals: np.ndarray, threads: int = 0) -> str:
         lay = csv_layout(self.meta, self.vocabs)

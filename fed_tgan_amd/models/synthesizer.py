@@ -89,6 +89,19 @@ class CTGANSynthesizer(BaseSynthesizer):
             return self.engine.generate_decoded_where(int(n), req, max_passes=max_passes).cpu().numpy()
         return self.engine.generate_decoded(n).cpu().numpy()
 
+    def sample_remaining_columns(self, known, mask=None, tries: int = 64, retries: int = 2, tol=None) -> np.ndarray:
+        """Complete partial rows: ``known`` [N, n_columns] holds the cells that are fixed, by column index and in the
+        model's decoded space as ``sample(where=)`` takes them (raw continuous values, category values as in the
+        training data); a NaN cell -- or, with ``mask`` [N, n_columns], a cell whose mask entry is 0 -- is to be
+        generated.  Returns [N, n_columns]: every row's known cells as given, the others from the closest of
+        ``tries`` rows generated under the row's own condition (models/known.py; the distances reached are in
+        ``engine.last_known``)."""
+        known = np.asarray(known, dtype=np.float64)
+        if known.ndim != 2:
+            raise ValueError("known must be [N, n_columns]")
+        mask = ~np.isnan(known) if mask is None else (np.asarray(mask) != 0)
+        return self.engine.generate_decoded_known(known, mask, tries=tries, retries=retries, tol=tol).cpu().numpy()
+
     def sample_encoded(self, n: int) -> np.ndarray:
         return self.engine.generate_encoded(n).cpu().numpy()
 

@@ -615,6 +615,22 @@ class HipOps:
         self.L.pred_mark(req["pred_j"], req["pred_kind"], req["pred_lo"], req["pred_hi"], req["pred_lut_off"],
                          req["pred_lut_len"], req["pred_lut"], req["pred_stats"], out, tgt)
 
+    # ------------------------------------------------------------------ completion of partial rows
+    KNOWN_MAX_TRIES = 1024     # kernels/launch.h KNOWN_MAX_TRIES
+
+    def known_request(self, qidx, drv_span, drv_opt, tries, col, opt, cond, h=None, c_col0=0):
+        """Same contract (and bit-identical results) as TorchOps.known_request (kernels/known_gen.hip
+        known_request_kernel).  h: only the fp32 activation buffer (a bf16 one holds no one-hot)."""
+        self.L.known_request(qidx, drv_span, drv_opt, int(tries), col, opt, h, int(c_col0), cond["cond_offset"],
+                             cond["cond_width"])
+
+    def known_match(self, known, mask, qidx, tries, cand, kind, scale, state, dst):
+        """Same contract as TorchOps.known_match (kernels/known_gen.hip known_match_kernel): one workgroup per slot,
+        the slot's candidates staged through LDS; the continuous sum is a chain of fused multiply-adds in column
+        order, so it rounds once per term where the torch op rounds twice.  Nothing is allocated."""
+        self.L.known_match(known, mask, qidx, int(tries), cand, kind, scale, state["best"], state["dc"],
+                           state["miss"], state["seen"], state["pick"], dst)
+
     # ------------------------------------------------------------------ similarity evaluator
     SIM_SORT_TILE = 2048   # kernels/launch.h SIM_SORT_TILE: keys per sorted LDS tile / merged output tile
 

@@ -500,6 +500,98 @@ class TorchOps:
         st[1] += int(rej.sum())
         st[2:2 + P] += torch.bincount(first[rej], minlength=P).to(st.dtype)
 
+    # ------------------------------------------------------------------ completion of partial rows
+    KNOWN_MAX_TRIES = 1024     # candidate rows per query and pass (kernels/launch.h KNOWN_MAX_TRIES)
+
+    def _known_tries(self, tries) -> int:
+        R = int(tries)
+        if not 1 <= R <= self.KNOWN_MAX_TRIES:
+            raise ValueError(f"tries must be 1..{self.KNOWN_MAX_TRIES}, got {tries}")
+        return R
+
+    def known_request(self, qidx, drv_span, drv_opt, tries, col, opt, cond, h=None, c_col0=0):
+        """Replace the generation sampler's conditions by those of the known rows a pass serves (models/known.py).
+
+        qidx int32 [q]: the query of slot s, -1 for an idle slot; slot s owns the rows s * tries .. s * tries + tries
+        - 1 of the pass.  drv_span / drv_opt int32 [queries]: the cond-span and option that drive a query, span -1
+        for none.  Every row of a slot with i = qidx[s] >= 0 and drv_span[i] >= 0 gets col = drv_span[i], opt =
+        drv_opt[i], and the hot element of h moves as in cond_request.  Rows of idle slots and of queries without a
+        driver keep what the sampler drew, and so do rows whose driver points outside the span tables.  No random
+        numbers are drawn."""
+        R = self._known_tries(tries)
+        m = int(qidx.numel()) * R
+        if m == 0:
+            return
+        i = qidx.long().repeat_interleave(R)
+        nq = int(drv_span.numel())
+        live = (i >= 0) & (i < nq)
+        ic = i.clamp(0, max(nq - 1, 0))
+        span = torch.where(live, drv_span.long()[ic], torch.full_like(i, -1)) if nq else torch.full_like(i, -1)
+        o = drv_opt.long()[ic] if nq else torch.zeros_like(i)
+        width = cond["cond_width"].long()
+        ok = (span >= 0) & (span < width.numel())
+        ok &= (o >= 0) & (o < width[span.clamp(0, width.numel() - 1)])
+        rows = torch.nonzero(ok).view(-1)
+        if rows.numel() == 0:
+            return
+        span, o = span[rows], o[rows]
+        if h is not None:
+            off = cond["cond_offset"].long()
+            h[rows, c_col0 + off[col[:m].long()[rows]] + opt[:m].long()[rows]] = 0.0
+            h[rows, c_col0 + off[span] + o] = 1.0
+        col[rows] = span.to(col.dtype)
+        opt[rows] = o.to(opt.dtype)
+
+    def known_match(self, known, mask, qidx, tries, cand, kind, scale, state, dst):
+        """Judge the candidates of a decoded pass against the known cells of the queries it serves.
+
+        known float64 / mask uint8 [queries, n_cols] (cell (i, j) is known iff mask[i, j] != 0; an unknown cell's
+        value is never read), qidx int32 [q], cand float64 [>= q * tries, n_cols], kind int32 [n_cols] (0
+        continuous, 1 categorical), scale float64 [n_cols], state: dict of best / dc float64, miss int32, seen / pick
+        int64, one entry per query.  For slot s with i = qidx[s] >= 0 and candidate t of its tries rows:
+        dc_t = the sum over the known continuous columns, in column order, of ((known - cand) * scale)^2, ms_t = the
+        known categorical columns whose codes differ, d2_t = dc_t + ms_t.  t* = the lowest t with the smallest d2
+        (a NaN distance never wins).  Iff d2_t* < best[i]: best / dc / miss take t*'s values, pick[i] = seen[i] +
+        t*, dst[i, j] = known[i, j] where known, else cand[t*, j].  In every case seen[i] += tries.  Idle slots write
+        nothing."""
+        R = self._known_tries(tries)
+        q = int(qidx.numel())
+        if q == 0:
+            return
+        n_cols = int(known.shape[1])
+        slots = torch.nonzero((qidx >= 0) & (qidx < known.shape[0])).view(-1)
+        if slots.numel() == 0:
+            return
+        i = qidx.long()[slots]
+        K = known[i]
+        M = mask[i] != 0
+        C = cand[:q * R].view(q, R, n_cols)[slots]
+        acc = torch.zeros(slots.numel(), R, dtype=torch.float64, device=known.device)
+        ms = torch.zeros(slots.numel(), R, dtype=torch.int32, device=known.device)
+        zero = torch.zeros((), dtype=torch.float64, device=known.device)
+        for j, kd in enumerate(kind.tolist()):
+            if not bool(M[:, j].any()):
+                continue
+            if kd == 0:
+                d = (K[:, j, None] - C[:, :, j]) * scale[j]
+                acc = acc + torch.where(M[:, j, None], d * d, zero)
+            else:
+                ms = ms + (M[:, j, None] & (C[:, :, j] != K[:, j, None])).to(torch.int32)
+        d2 = acc + ms.double()
+        d2 = torch.where(torch.isnan(d2), torch.full_like(d2, float("inf")), d2)
+        least = d2.min(1).values
+        t = torch.arange(R, device=known.device)
+        ts = torch.where(d2 == least[:, None], t, torch.full_like(t, R)).min(1).values
+        rows = torch.arange(slots.numel(), device=known.device)
+        upd = least < state["best"][i]
+        iu, ru, tu = i[upd], rows[upd], ts[upd]
+        state["best"][iu] = least[upd]
+        state["dc"][iu] = acc[ru, tu]
+        state["miss"][iu] = ms[ru, tu]
+        state["pick"][iu] = state["seen"][iu] + tu
+        dst[iu] = torch.where(M[ru], K[ru], C[ru, tu])
+        state["seen"][i] += R
+
     # ------------------------------------------------------------------ similarity evaluator
     SIM_SORT_TILE = 2048   # the HIP sort's tile; no meaning here beyond the shared attribute
     SIM_PLAIN, SIM_NONNEG, SIM_CAT = 0, 1, 2
